@@ -17,15 +17,29 @@ statuses to rank 0 over xGMI -- issued on a second stream so that step k's gathe
 step k+1's decode (double-buffered outputs; the closing synchronize waits for the last
 one).  Inputs are resident in HBM before the timed region.
 
-After the timed region (never inside it):
+A plain run does only what the headline needs: set-up, warmup, the K timed steps, the
+--dump-outputs files if asked for, and the JSON line (its roofline keys come from the timed
+steps' own HIP-event kernel times and a committed PMC summary, no extra run).
+
+--dump-outputs DIR writes, after the timed steps, what the LAST timed step returned (on rank 0,
+for N>1 the gathered result of all ranks): DIR/score.npy (f64, every sequence), DIR/status.npy
+(f32, every sequence), DIR/path.npy (f32 [k, T]: the state paths of the k sequences listed in
+DIR/path_sequences.npy, f64 -- every sequence up to 16,384, else a fixed seeded sample of
+16,384, 33.5 MB).  The inputs are seeded, so two runs with the same arguments decode the same
+batch and two builds can be compared file for file.
+
+--full adds, after the timed region (never inside it):
 * N>1: rank 0 assembles the LAST step's gathered result and compares it bit for bit (paths,
   scores, statuses) with its own single-GPU decode of the same global batch -> "verified";
+* the f32 trellis of the same batch, timed like the headline -> `f32_trellis`;
+* N>1: config 5 sharded over the ranks -> `c5_sharded`;
 * rank 0: the CPU baseline (the oracle, test infrastructure, timed on this host) whose leg
   also checks the GPU's first sequences against the oracle's f64 row-A0 decode;
 * rank 0: configs 2, 3 and 5 (BASELINE.json configs[1], [2], [4]) on its GPU, inputs
   resident, as the extra key `configs` (--no-configs skips them).
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak] [--dtype f64|f32]
+                       [--dump-outputs DIR] [--full]
        (N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N)
 Rank 0 prints ONE JSON line.
 """
@@ -74,17 +88,50 @@ def parse():
     p.add_argument("--dtype", choices=("f64", "f32"), default="f64",
                    help="f64 (default): the exact-f64 trellis, paths and scores bit-identical to the "
                         "f64 reference recurrence; f32: the f32 trellis + f64 re-score of each path")
-    p.add_argument("--no-f32-extra", action="store_true", help="skip the f32-trellis extra measurement")
-    p.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample budget")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-configs", action="store_true", help="skip the configs 2/3/5 extra measurements")
-    p.add_argument("--no-verify", action="store_true", help="N>1: skip rank 0's re-decode of the global batch")
-    p.add_argument("--c5-batch", type=int, default=B_TOTAL, help="N>1: sequences of the sharded config-5 leg")
-    p.add_argument("--no-c5-sharded", action="store_true", help="N>1: skip the sharded config-5 leg")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last step's result (score, status, a seeded sample "
+                        "of the paths) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the extra legs: the f32 trellis, the CPU baseline and "
+                        "its oracle check, configs 2/3/5, and for N>1 rank 0's verify decode and the sharded "
+                        "config 5 (the --no-* options below drop single legs of --full)")
+    p.add_argument("--no-f32-extra", action="store_true", help="--full: skip the f32-trellis extra measurement")
+    p.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU baseline sample budget")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and its check")
+    p.add_argument("--no-configs", action="store_true", help="--full: skip the configs 2/3/5 extra measurements")
+    p.add_argument("--no-verify", action="store_true", help="--full, N>1: skip rank 0's re-decode of the global batch")
+    p.add_argument("--c5-batch", type=int, default=B_TOTAL, help="--full, N>1: sequences of the sharded config-5 leg")
+    p.add_argument("--no-c5-sharded", action="store_true", help="--full, N>1: skip the sharded config-5 leg")
     p.add_argument("--backend", choices=("nccl", "gloo"), default="nccl",
                    help="collective backend for N>1 (nccl = RCCL over xGMI; gloo only to rehearse the "
                         "multi-rank path with several ranks on one GPU)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_PATH_SEQS = 16384       # --dump-outputs: sequences whose paths are written (x T x 4 B = 33.5 MB)
+
+
+def dump_outputs(dirname, path, score, status, nseq):
+    """--dump-outputs: the decode result a caller receives (torch tensors: path int32 [nseq*T],
+    score f64 [nseq], status u8 [nseq]) as .npy files: every score and status, and the paths of
+    a fixed sample of sequences (all of them up to DUMP_PATH_SEQS; the sample depends on SEED
+    and nseq alone, so it is the same from run to run and from build to build)."""
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    if nseq > DUMP_PATH_SEQS:
+        seqs = np.sort(np.random.default_rng(SEED).choice(nseq, size=DUMP_PATH_SEQS, replace=False))
+    else:
+        seqs = np.arange(nseq)
+    idx = torch.from_numpy(seqs.astype(np.int64)).to(path.device)
+    rows = path.view(nseq, T_LEN).index_select(0, idx)
+    np.save(os.path.join(dirname, "path.npy"), rows.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(dirname, "path_sequences.npy"), seqs.astype(np.float64))
+    np.save(os.path.join(dirname, "score.npy"), score.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(dirname, "status.npy"), status.cpu().numpy().astype(np.float32))
 
 
 def cpu_baseline(pi, a, b, obs_rank, budget_s, gpu_first):
@@ -454,19 +501,29 @@ def main():
     # this rank's first sequences as the timed run decoded them (for the CPU baseline's check)
     kc = min(64, nloc)
     pb, sb, stb = outs[last["buf"]]
-    first = (pb[: kc * T_LEN].cpu().numpy(), sb[:kc].cpu().numpy(), stb[:kc].cpu().numpy()) if f64 else None
+    first = ((pb[: kc * T_LEN].cpu().numpy(), sb[:kc].cpu().numpy(), stb[:kc].cpu().numpy())
+             if f64 and args.full else None)
+
+    # ---- rank 0, N>1: the last timed step's gathered result of all ranks (paths, scores, statuses)
+    glast = None
+    do_verify = world > 1 and args.full and not args.no_verify
+    if world > 1 and rank == 0 and (args.dump_outputs or do_verify):
+        parts = last["gather"]
+        ns = [cvd.shard_range(B, world, r)[1] - cvd.shard_range(B, world, r)[0] if args.scaling == "strong"
+              else args.batch for r in range(world)]
+        glast = (cvd.assemble([x[0] for x in parts], [n * T_LEN for n in ns]),
+                 cvd.assemble([x[1] for x in parts], ns), cvd.assemble([x[2] for x in parts], ns))
+
+    # ---- --dump-outputs: what the last timed step returned, before any --full leg reuses the buffers
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *(glast or (pb, sb, stb)), B if world > 1 else nloc)
 
     # ---- rank 0 re-decodes the global batch on its own GPU: the gathered last step must equal it
     verify = None
-    if world > 1 and not args.no_verify:
+    if do_verify:
         ok = True
         if rank == 0:
-            parts = last["gather"]
-            ns = [cvd.shard_range(B, world, r)[1] - cvd.shard_range(B, world, r)[0] if args.scaling == "strong"
-                  else args.batch for r in range(world)]
-            gp = cvd.assemble([x[0] for x in parts], [n * T_LEN for n in ns])
-            gs = cvd.assemble([x[1] for x in parts], ns)
-            gst = cvd.assemble([x[2] for x in parts], ns)
+            gp, gs, gst = glast
             obs_g = torch.from_numpy(synth.iid_obs(V_OBS, B * T_LEN, SEED)).to(dev)
             off_gh = np.arange(B + 1, dtype=np.int64) * T_LEN
             rp = torch.empty(B * T_LEN, dtype=torch.int32, device=dev)
@@ -488,7 +545,7 @@ def main():
             dist.barrier()
 
     f32_extra = None
-    if f64 and not args.no_f32_extra:
+    if f64 and args.full and not args.no_f32_extra:
         p64 = outs[last["buf"]][0].clone()  # the f64 (reference-exact) paths of this rank's shard
         el32, kt32, _ = timed("f32", args.steps, args.warmup)
         # measured, not quoted: the share of this rank's sequences whose f32 path differs from
@@ -506,7 +563,7 @@ def main():
                              "f64 (reference-exact) path of the same batch"}
 
     c5s = None
-    if world > 1 and not args.no_c5_sharded:
+    if world > 1 and args.full and not args.no_c5_sharded:
         c5s = c5_sharded(dev, world, rank, dist, args.backend, args.c5_batch, 2, ph)
 
     # per-rank peak device memory: torch's tensors + the library's tables and workspaces
@@ -560,6 +617,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": ms_step,
         "higher_is_better": True,
         "scaling": args.scaling,
@@ -609,10 +667,10 @@ def main():
         out["multi_gpu_check"] = verify
     if c5s is not None:
         out["c5_sharded"] = c5s
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(pi, a, b, obs, args.cpu_seconds, first)
         out["cpu_baseline"]["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
-    if rank == 0 and not args.no_configs:
+    if rank == 0 and args.full and not args.no_configs:
         out["configs"] = bench_configs(dev, stream)
     checks = []
     if verify is not None:
@@ -621,7 +679,7 @@ def main():
         checks.append(c5s["check"]["equal"])
     if out.get("cpu_baseline", {}).get("check"):
         checks.append(out["cpu_baseline"]["check"]["bit_exact"])
-    out["verified"] = bool(checks) and all(checks)
+    out["verified"] = (bool(checks) and all(checks)) if args.full else None  # a plain run checks nothing
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:

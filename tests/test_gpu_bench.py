@@ -15,12 +15,14 @@ from conftest import ROOT
 pytestmark = pytest.mark.gpu
 
 
-def test_bench_two_rank_rehearsal(gpu):
+def test_bench_two_rank_rehearsal(gpu, tmp_path):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
+    dump = str(tmp_path / "dump")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29561", os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2048", "--backend", "gloo",
-           "--no-f32-extra", "--no-configs", "--cpu-seconds", "1", "--c5-batch", "2048"]
+           "--full", "--no-f32-extra", "--no-configs", "--cpu-seconds", "1", "--c5-batch", "2048",
+           "--dump-outputs", dump]
     # own session: on a timeout the launcher AND its ranks are killed (process group)
     p = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, cwd=ROOT,
                          start_new_session=True)
@@ -48,3 +50,24 @@ def test_bench_two_rank_rehearsal(gpu):
     r = d["roofline"]
     assert r["bound"] == "valu" and 0 < r["frac"] < 1 and r["frac_f64_bytes"] > r["frac"]
     assert r["roofs"]["valu"]["frac"] > 0
+    # --dump-outputs: rank 0 wrote the gathered last step (both shards) -- every sequence here,
+    # the batch being below the path sample's size -- and it is the f64 oracle's row-A0 decode
+    import c_oracle
+    import numpy as np
+
+    import bench
+    from cviterbi import synth
+
+    got = {k: np.load(os.path.join(dump, k + ".npy")) for k in ("path", "path_sequences", "score", "status")}
+    assert got["path"].dtype == np.float32 and got["path"].shape == (2048, bench.T_LEN)
+    assert got["score"].dtype == np.float64 and got["status"].dtype == np.float32
+    assert np.array_equal(got["path_sequences"], np.arange(2048, dtype=np.float64))
+    pi, a, b = synth.random_hmm(bench.N_STATES, bench.V_OBS, seed=bench.SEED)
+    assert not got["status"].any() and np.isfinite(got["score"]).all()
+    for s0 in (0, 2048 - 128):  # the head of rank 0's shard and the tail of rank 1's
+        off = np.arange(129, dtype=np.int64) * bench.T_LEN
+        obs = synth.iid_obs(bench.V_OBS, 128 * bench.T_LEN, bench.SEED, start=s0 * bench.T_LEN)
+        rp, rs, rst = c_oracle.decode_batch(pi, a, b, off, obs, c_oracle.VITERBI, np.float64, nthreads=8)
+        assert np.array_equal(got["path"][s0:s0 + 128].reshape(-1), rp.astype(np.float32))
+        assert np.array_equal(got["score"][s0:s0 + 128].view(np.int64), rs.view(np.int64))
+        assert np.array_equal(got["status"][s0:s0 + 128], rst.astype(np.float32))

@@ -11,7 +11,7 @@ for G in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU" \
          "SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_SALU"; do
   i=$((i + 1))
   timeout -k 10 ${T_PMC:-300} rocprofv3 --pmc $G --kernel-include-regex "${KREGEX:-trellis_fwd}" -d $OUT/g$i -o p \
-    --output-format csv -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-} \
+    --output-format csv -- python3 $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-} \
     > $OUT/g$i.log 2>&1 || exit $?
 done
 python3 - "$OUT" <<'PY' > $OUT/summary.txt

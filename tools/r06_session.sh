@@ -74,9 +74,9 @@ run() {
             python3 -u tools/bench_configs.py c4f64 || return $?
       done ;;
     smoke) step smoke 200 python3 -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" ;;
-    bench) step bench 400 python3 -u bench.py ;;
+    bench) step bench 400 python3 -u bench.py --full ;;
     prof)
-      (cd /tmp && step prof 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o prof -- python3 $R/bench.py --no-f32-extra) ;;
+      (cd /tmp && step prof 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o prof -- python3 $R/bench.py --full --no-f32-extra) ;;
     *) echo "unknown step $1"; return 2 ;;
   esac
 }
