@@ -35,6 +35,7 @@
 #include "kernels/cfn.h"
 #include "kernels/exact.h"
 #include "kernels/fit.h"
+#include "kernels/posterior.h"
 #include "kernels/trellis.h"
 #include "kernels/trellis64.h"
 #include "tuning.h"
@@ -249,6 +250,14 @@ struct cv_hmm {
   bool g32_ready = false;
   DevBuf d_pi32, d_a32, d_et32;
   DevBuf d_at32;  // [N][N] a^T f32 (generic_bt_rows)
+  // probability-space tables of the posterior kernels (10^x, zero padded to pnp states; built on
+  // first use): pi[pnp], a[pnp][pnp], a^T, et[V][pnp], and the dump rows of masked stores
+  int pnp = 0;
+  DevBuf p_pi, p_a, p_at, p_et, p_dump;
+  // posterior workspace: the scaled forward rows of one chunk, the longest-first order, and the
+  // host API's gamma staging
+  DevBuf ps_rows, ps_order, st_gamma;
+  OrderStage ps_pin;
   // workspace
   DevBuf ws_main, ws_last, ws_order;
   // a second decode workspace + stream: the constrained decode's unconstrained sequences run
@@ -1270,6 +1279,172 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
   return CV_OK;
 }
 
+// ---- posterior (sum-product) path: cv_posterior_batch* --------------------------------------
+// Probability-space tables of the posterior kernels: p = 10^x by the host's correctly rounded
+// pow (-inf -> 0 exactly), zero padded to pnp states so the kernels never test a row or column
+// against N; the emission column of each observation is contiguous ([V][pnp]).
+cv_status ensure_post_tables(cv_hmm* h) {
+  const int np = cvp::post_padded_states(h->N);
+  if (h->pnp == np) return CV_OK;
+  const int N = h->N;
+  const int64_t V = h->V;
+  auto p10 = [](double x) { return x == -INFINITY ? 0.0 : std::pow(10.0, x); };
+  std::vector<double> pi((size_t)np, 0.0), a((size_t)np * np, 0.0), at((size_t)np * np, 0.0), et((size_t)V * np, 0.0);
+  for (int i = 0; i < N; ++i) pi[(size_t)i] = p10(h->pi[(size_t)i]);
+  parallel_ranges(N, [&](int, int64_t lo, int64_t hi) {
+    for (int64_t i = lo; i < hi; ++i)
+      for (int j = 0; j < N; ++j) {
+        const double v = p10(h->a[(size_t)i * N + j]);
+        a[(size_t)i * np + j] = v;
+        at[(size_t)j * np + i] = v;
+      }
+  }, std::max<int64_t>(1, 4096 / N));
+  parallel_ranges(N, [&](int, int64_t lo, int64_t hi) {
+    for (int64_t i = lo; i < hi; ++i)
+      for (int64_t o = 0; o < V; ++o) et[(size_t)o * np + i] = p10(h->b[(size_t)i * V + o]);
+  }, std::max<int64_t>(1, 4096 / std::max<int64_t>(V, 1)));
+  cv_status st;
+  if ((st = upload(h->p_pi, pi.data(), pi.size() * 8)) != CV_OK) return st;
+  if ((st = upload(h->p_a, a.data(), a.size() * 8)) != CV_OK) return st;
+  if ((st = upload(h->p_at, at.data(), at.size() * 8)) != CV_OK) return st;
+  if ((st = upload(h->p_et, et.data(), et.size() * 8)) != CV_OK) return st;
+  if ((st = h->p_dump.ensure((size_t)cvp::kPostDumpWaves * 64 * 8)) != CV_OK) return st;
+  h->pnp = np;
+  return CV_OK;
+}
+
+// Core of cv_posterior_batch*: all pointers are device pointers except offsets_host.  Chunks of
+// whole sequences (original order) whose forward rows fit the workspace cap run forward then
+// backward on `stream`; scoring mode (no path, no gamma) is one forward launch with no rows.
+cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, const int64_t* offsets_dev,
+                           const int32_t* obs_dev, const cv_opts& o, double* loglik_dev, int32_t* path_dev,
+                           double* gamma_dev, uint8_t* status_dev, hipStream_t stream) {
+  if (o.dtype == CV_DTYPE_F32) return set_err(CV_EUNSUPPORTED, "the posterior path is f64 only");
+  if (o.dtype != CV_DTYPE_F64) return set_err(CV_EINVAL, "bad dtype %d", o.dtype);
+  if (o.assoc != CV_ASSOC_VITERBI)
+    return set_err(CV_EINVAL, "the posterior path reads the model as the VITERBI association (assoc %d)", o.assoc);
+  if (o.kernel != CV_KERNEL_AUTO && o.kernel != CV_KERNEL_GENERIC)
+    return set_err(CV_EINVAL, "posterior kernel must be AUTO or GENERIC (kernel %d)", o.kernel);
+  if (h->N > cvp::kPostMaxStates)
+    return set_err(CV_EUNSUPPORTED, "the posterior kernels cover N <= %d (N=%d)", cvp::kPostMaxStates, h->N);
+  const bool generic = o.kernel == CV_KERNEL_GENERIC || h->N > cvp::kPostMmStates;
+  std::vector<int64_t> off_copy;
+  if (!offsets_host) {
+    off_copy.resize((size_t)nseq + 1);
+    HIP_TRY(hipMemcpyAsync(off_copy.data(), offsets_dev, off_copy.size() * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    offsets_host = off_copy.data();
+  }
+  cv_status st = check_batch(h, nseq, offsets_host);
+  if (st != CV_OK) return st;
+  if ((st = ensure_post_tables(h)) != CV_OK) return st;
+  const int np = h->pnp;
+  h->last_launches = 0;
+  h->last_kernel = generic ? CV_KERNEL_GENERIC : CV_KERNEL_AUTO;
+  h->last_np = np;
+  h->last_mt = generic ? -1 : cvp::kPostGroup;
+  if (nseq == 0) return CV_OK;
+  if (h->ws_rec) HIP_TRY(hipStreamWaitEvent(stream, h->ws_done, 0));
+
+  const bool store = path_dev || gamma_dev;
+  const uint64_t per_elem = (uint64_t)np * 8;
+  std::vector<std::pair<int64_t, int64_t>> chunks;
+  uint64_t max_elems = 0;
+  if (!store) {
+    chunks.emplace_back(0, nseq);
+  } else {
+    // 2 KiB of rows per element at N = 256: the f64 trellis's default cap (HBM3E: 288 GB per GPU)
+    const uint64_t cap = o.workspace_bytes ? o.workspace_bytes : default_workspace_cap(h->ps_rows.bytes, kDefaultWorkspaceT64);
+    const uint64_t elem_cap = std::max<uint64_t>(cap / per_elem, 1);
+    // equal shares rather than full chunks and a remainder: every launch fills the device alike
+    const uint64_t total_elems = (uint64_t)(offsets_host[nseq] - offsets_host[0]);
+    const uint64_t nchunks = std::max<uint64_t>(1, (total_elems + elem_cap - 1) / elem_cap);
+    const uint64_t target = std::max<uint64_t>(1, (total_elems + nchunks - 1) / nchunks);
+    for (int64_t s0 = 0; s0 < nseq;) {
+      int64_t s1 = s0;
+      uint64_t elems = 0;
+      while (s1 < nseq && s1 - s0 < (1 << 30)) {
+        const uint64_t T = (uint64_t)(offsets_host[s1 + 1] - offsets_host[s1]);
+        if (s1 > s0 && (elems + T > elem_cap || elems + T > target)) break;
+        elems += T;
+        ++s1;
+      }
+      max_elems = std::max(max_elems, elems);
+      chunks.emplace_back(s0, s1);
+      s0 = s1;
+    }
+    if ((st = h->ps_rows.ensure((size_t)std::max<uint64_t>(max_elems, 1) * per_elem)) != CV_OK) return st;
+  }
+  // longest first inside each chunk (stable), so a group's sequences have similar lengths
+  const int32_t* order_dev = nullptr;
+  bool varlen = false;
+  const int64_t T0 = offsets_host[1] - offsets_host[0];
+  for (int64_t s = 1; s < nseq && !varlen; ++s) varlen = (offsets_host[s + 1] - offsets_host[s]) != T0;
+  if (varlen) {
+    if (nseq > INT32_MAX) return set_err(CV_EINVAL, "too many sequences (%lld)", (long long)nseq);
+    std::vector<int32_t>& ord = h->order_host;
+    ord.resize((size_t)nseq);
+    std::iota(ord.begin(), ord.end(), 0);
+    auto len = [&](int32_t x) { return offsets_host[x + 1] - offsets_host[x]; };
+    for (const auto& c : chunks)
+      std::stable_sort(ord.begin() + c.first, ord.begin() + c.second, [&](int32_t x, int32_t y) { return len(x) > len(y); });
+    if ((st = h->ps_order.ensure((size_t)nseq * 4)) != CV_OK) return st;
+    int32_t* pin = h->ps_pin.acquire((size_t)nseq);
+    if (!pin) return set_err(CV_ENOMEM, "pinned staging of %lld order entries failed", (long long)nseq);
+    std::memcpy(pin, ord.data(), (size_t)nseq * 4);
+    HIP_TRY(hipMemcpyAsync(h->ps_order.p, pin, (size_t)nseq * 4, hipMemcpyHostToDevice, stream));
+    HIP_TRY(h->ps_pin.release(stream));
+    order_dev = h->ps_order.as<int32_t>();
+  }
+  const size_t nev = 4 * chunks.size();
+  if (h->acc_on && h->acc_used + nev > kMaxTimedEvents) h->acc_on = false, h->acc_overflow = true;
+  const size_t eb = h->acc_on ? h->acc_used : 0;
+  h->last_ev_base = eb;
+  for (size_t i = 0; i < nev; ++i)
+    if (!get_event(h->ev, eb + i)) return set_err(CV_EDEVICE, "hipEventCreate failed");
+  for (size_t ci = 0; ci < chunks.size(); ++ci) {
+    const auto& c = chunks[ci];
+    cvp::PostArgs g{};
+    g.pi = h->p_pi.as<double>();
+    g.a = h->p_a.as<double>();
+    g.at = h->p_at.as<double>();
+    g.et = h->p_et.as<double>();
+    g.offsets = offsets_dev;
+    g.obs = obs_dev;
+    g.forced = o.forced;
+    g.order = order_dev;
+    g.seq_begin = c.first;
+    g.seq_end = c.second;
+    g.elem_base = offsets_host[c.first];
+    g.nstates = h->N;
+    g.np = np;
+    g.nobs = h->V;
+    g.rows = store ? h->ps_rows.as<double>() : nullptr;
+    g.loglik = loglik_dev;
+    g.status = status_dev;
+    g.path = path_dev;
+    g.gamma = gamma_dev;
+    g.dump = h->p_dump.as<double>();
+    hipEvent_t f0 = h->ev[eb + 4 * ci], f1 = h->ev[eb + 4 * ci + 1], b0 = h->ev[eb + 4 * ci + 2], b1 = h->ev[eb + 4 * ci + 3];
+    HIP_TRY(hipEventRecord(f0, stream));
+    hipError_t err = cvp::launch_post_fwd(g, generic, stream);
+    if (err != hipSuccess) return set_err(CV_EDEVICE, "posterior forward launch failed: %s", hipGetErrorString(err));
+    HIP_TRY(hipEventRecord(f1, stream));
+    HIP_TRY(hipEventRecord(b0, stream));
+    if (store) {
+      err = cvp::launch_post_bwd(g, generic, stream);
+      if (err != hipSuccess) return set_err(CV_EDEVICE, "posterior backward launch failed: %s", hipGetErrorString(err));
+    }
+    HIP_TRY(hipEventRecord(b1, stream));
+    h->last_launches = (int64_t)ci + 1;
+  }
+  if (h->acc_on) h->acc_used += nev;
+  if (!h->ws_done) HIP_TRY(hipEventCreateWithFlags(&h->ws_done, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(h->ws_done, stream));
+  h->ws_rec = true;
+  return CV_OK;
+}
+
 cv_opts default_opts() {
   cv_opts o;
   cv_opts_init(&o);
@@ -1368,7 +1543,8 @@ CV_API cv_status cv_hmm_release_workspaces(cv_hmm* h) {
                     &h->chainb.off, &h->chainb.obs, &h->chainb.path, &h->chainb.res, &h->chainb.cert, &h->chainb.ebin,
                     &h->chainb.q, &h->chainb.ends, &h->chainb.gid, &h->chainb.gpath, &h->chainb.first,
                     &h->chainb.rpsi, &h->chainb.rows, &h->chainb.small, &h->chainb.rpath, &h->chainb.soff,
-                    &h->chainb.sobs, &h->chainb.spath, &h->chainb.sres, &h->chainb.sinit, &h->chainb.slast})
+                    &h->chainb.sobs, &h->chainb.spath, &h->chainb.sres, &h->chainb.sinit, &h->chainb.slast, &h->ps_rows,
+                    &h->ps_order, &h->st_gamma})
     b->release();
   h->ws_rec = false;
   h->side.ws_rec = false;
@@ -1516,6 +1692,81 @@ CV_API cv_status cv_decode_batch(cv_hmm* h, int64_t nseq, const int64_t* offsets
   cv_status st = set_device(h);
   if (st != CV_OK) return st;
   return decode_host_locked(h, nseq, offsets, obs, opts ? *opts : default_opts(), path_out, score_out, status_out);
+}
+
+CV_API cv_status cv_posterior_batch_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
+                                           const int64_t* offsets_dev, const int32_t* obs_dev, const cv_opts* opts,
+                                           double* loglik_dev, int32_t* path_dev, double* gamma_dev,
+                                           uint8_t* status_dev) {
+  if (!h) return set_err(CV_EINVAL, "null handle");
+  if (nseq < 0) return set_err(CV_EINVAL, "nseq < 0");
+  if (nseq > 0 && (!offsets_dev || !obs_dev || !loglik_dev || !status_dev))
+    return set_err(CV_EINVAL, "null device buffer");
+  CV_LOCK(h);
+  cv_status st = set_device(h);
+  if (st != CV_OK) return st;
+  const cv_opts o = opts ? *opts : default_opts();
+  hipStream_t stream = o.stream ? (hipStream_t)o.stream : h->stream;
+  return posterior_device(h, nseq, offsets_host, offsets_dev, obs_dev, o, loglik_dev, path_dev, gamma_dev, status_dev,
+                          stream);
+}
+
+CV_API cv_status cv_posterior_batch(cv_hmm* h, int64_t nseq, const int64_t* offsets, const int32_t* obs,
+                                    const cv_opts* opts, double* loglik_out, int32_t* path_out, double* gamma_out,
+                                    uint8_t* status_out) {
+  if (!h) return set_err(CV_EINVAL, "null handle");
+  if (nseq < 0 || (nseq > 0 && (!offsets || !obs || !loglik_out || !status_out)))
+    return set_err(CV_EINVAL, "null argument");
+  CV_LOCK(h);
+  cv_status st = set_device(h);
+  if (st != CV_OK) return st;
+  cv_opts o = opts ? *opts : default_opts();
+  if (nseq == 0) return CV_OK;
+  if ((st = check_batch(h, nseq, offsets)) != CV_OK) return st;
+  const int64_t base = offsets[0], total = offsets[nseq];
+  const int64_t N = h->N;
+  hipStream_t stream = o.stream ? (hipStream_t)o.stream : h->stream;
+  if ((st = h->st_off.ensure((size_t)(nseq + 1) * 8)) != CV_OK) return st;
+  if ((st = h->st_obs.ensure((size_t)std::max<int64_t>(total, 1) * 4)) != CV_OK) return st;
+  if (path_out && (st = h->st_path.ensure((size_t)std::max<int64_t>(total, 1) * 4)) != CV_OK) return st;
+  if (gamma_out && (st = h->st_gamma.ensure((size_t)std::max<int64_t>(total, 1) * N * 8)) != CV_OK) return st;
+  if ((st = h->st_score.ensure((size_t)nseq * 8)) != CV_OK) return st;
+  if ((st = h->st_status.ensure((size_t)nseq)) != CV_OK) return st;
+  HIP_TRY(hipMemcpyAsync(h->st_off.p, offsets, (size_t)(nseq + 1) * 8, hipMemcpyHostToDevice, stream));
+  // the observations are range-checked on the device (CV_SEQ_BADOBS), as in the _device variant
+  if (total > base)
+    HIP_TRY(hipMemcpyAsync(h->st_obs.as<int32_t>() + base, obs + base, (size_t)(total - base) * 4,
+                           hipMemcpyHostToDevice, stream));
+  if (o.forced) {
+    const int32_t* fr = o.forced;
+    const int64_t k = first_bad(base, total, [&](int64_t i) { return fr[i] < -1 || fr[i] >= N; });
+    if (k >= 0) return set_err(CV_EINVAL, "forced[%lld] = %d out of range [-1,%d)", (long long)k, fr[k], h->N);
+    if ((st = h->st_forced.ensure((size_t)std::max<int64_t>(total, 1) * 4)) != CV_OK) return st;
+    if (total > base)
+      HIP_TRY(hipMemcpyAsync(h->st_forced.as<int32_t>() + base, fr + base, (size_t)(total - base) * 4,
+                             hipMemcpyHostToDevice, stream));
+    o.forced = h->st_forced.as<int32_t>();
+  }
+  st = posterior_device(h, nseq, offsets, h->st_off.as<int64_t>(), h->st_obs.as<int32_t>(), o, h->st_score.as<double>(),
+                        path_out ? h->st_path.as<int32_t>() : nullptr, gamma_out ? h->st_gamma.as<double>() : nullptr,
+                        h->st_status.as<uint8_t>(), stream);
+  if (st != CV_OK) {
+    (void)hipStreamSynchronize(stream);
+    return st;
+  }
+  if (path_out && total > base)
+    HIP_TRY(hipMemcpyAsync(path_out + base, h->st_path.as<int32_t>() + base, (size_t)(total - base) * 4,
+                           hipMemcpyDeviceToHost, stream));
+  if (gamma_out && total > base)
+    HIP_TRY(hipMemcpyAsync(gamma_out + base * N, h->st_gamma.as<double>() + base * N, (size_t)(total - base) * N * 8,
+                           hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(loglik_out, h->st_score.p, (size_t)nseq * 8, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(status_out, h->st_status.p, (size_t)nseq, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  for (int64_t s = 0; s < nseq; ++s)
+    if (status_out[s] == CV_SEQ_INFEASIBLE)
+      return set_err(CV_EINFEASIBLE, "sequence %lld has likelihood 0", (long long)s);
+  return CV_OK;
 }
 
 // ---- consistency-constrained decode --------------------------------------------------------

@@ -42,6 +42,7 @@ EXPORTS = [
     "cv_solver_get_name", "cv_solver_get_explored_nodes", "cv_solver_destroy",
     "cv_hmm_fit_mle", "cv_hmm_fit_train", "cv_solver_write_cfn",
     "cv_hmm_set_tuning", "cv_hmm_get_tuning", "cv_tuning_key", "cv_hmm_release_workspaces",
+    "cv_posterior_batch", "cv_posterior_batch_device",
 ]
 
 
@@ -119,6 +120,8 @@ def lib():
         "cv_hmm_emit_probs": ([P, I64, P], S),
         "cv_decode_batch": ([P, I64, P, P, P, P, P, P], S),
         "cv_decode_batch_device": ([P, I64, P, P, P, P, P, P, P], S),
+        "cv_posterior_batch": ([P, I64, P, P, P, P, P, P, P], S),
+        "cv_posterior_batch_device": ([P, I64, P, P, P, P, P, P, P, P], S),
         "cv_last_timing": ([P, P], S),
         "cv_timing_begin": ([P], S),
         "cv_timing_end": ([P, P], S),

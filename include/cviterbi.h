@@ -211,8 +211,8 @@ CV_API void cv_hmm_destroy(cv_hmm* h);
  *                         per-sequence E-step kernels / the xi GEMM path at every N
  * Unknown keys and values outside int32 are CV_EINVAL.  cv_tuning_key(i) lists the keys
  * (NULL past the last). */
-/* Frees the handle's decode workspaces (delta rows, the constrained decode's and the parallel
- * chain's per-call buffers, pinned staging), which are otherwise kept grow-only between calls
+/* Frees the handle's decode workspaces (delta rows, the posterior path's forward rows, the
+ * constrained decode's and the parallel chain's per-call buffers, pinned staging), which are otherwise kept grow-only between calls
  * so repeated calls do not reallocate: e.g. ~1 GB of chain buffers (observations, paths, the
  * speculative batches' psi rows) and 18 MiB of pinned staging plus the 34-69 GB delta workspace
  * after a config-4-sized cv_decode_superseq_cp / cv_decode_batch.  The model tables
@@ -376,6 +376,51 @@ CV_API cv_status cv_decode_superseq_cp(cv_hmm* h, int64_t nseq, const int64_t* o
  * sequences whose paths the host walk fetched packed while the whole path copy ran beside it,
  * out[8] = walk steps that had to wait for that copy (a prediction miss; 0 when it held). */
 CV_API cv_status cv_last_superseq_stats(const cv_hmm* h, int64_t* out);
+
+/* ---- evaluation: sequence log-likelihood and posterior state marginals -------------------
+ * The sum-product counterpart of cv_decode_batch on the standard HMM, the model read as the
+ * row-A0 (VITERBI) association reads it with table entries p = 10^x (-inf = 0):
+ *   P(o, s) = pi[s_0] b[s_0, o_0] prod_t a[s_t-1, s_t] b[s_t, o_t].
+ * Per sequence: loglik_out[k] = log10 sum_s P(o, s); gamma_out[e * N + j] = P(s_t = j | o) for
+ * element e (element-major, N per element); path_out[e] = the first index of max_j gamma
+ * (posterior / max-marginal decoding).  path_out and gamma_out are nullable: with both NULL
+ * only the forward pass runs and no row is stored (scoring mode); otherwise the scaled forward
+ * rows go to the handle's workspace (NP * 8 bytes per element, NP = N rounded up to a multiple
+ * of 64; chunks of whole sequences under opts->workspace_bytes, 0 = default 64 GiB;
+ * cv_hmm_release_workspaces frees them) and one backward pass writes the argmax, and gamma
+ * only when asked for.
+ * opts: dtype CV_DTYPE_F64 (CV_DTYPE_F32 is CV_EUNSUPPORTED); assoc CV_ASSOC_VITERBI (others
+ * CV_EINVAL); kernel CV_KERNEL_AUTO (N <= 256: 32 sequences per workgroup in lock step, each
+ * step a product on the f64 matrix cores) or CV_KERNEL_GENERIC (one workgroup per sequence, an
+ * A/B knob and the kernel of every N > 256), CV_KERNEL_TRELLIS* is CV_EINVAL; forced as in
+ * cv_decode_batch: a forced element admits only its state, loglik becomes the joint
+ * log10 P(o, forced tags) and gamma is conditioned on the tags.  N <= 4096 (above:
+ * CV_EUNSUPPORTED).
+ * status_out: CV_SEQ_OK; CV_SEQ_EMPTY (loglik 0); CV_SEQ_BADOBS (an observation outside
+ * [0, V), checked on the device by both variants: loglik NaN, path -1, gamma rows 0; the call
+ * itself still returns CV_OK); CV_SEQ_INFEASIBLE (likelihood 0: loglik -inf, path -1, gamma
+ * rows 0).  No sequence disturbs another.  The host variant returns CV_EINFEASIBLE, after
+ * writing every output, when a sequence is infeasible.
+ * Numerics: the probability-space tables are built once per handle on first use (they count
+ * in cv_device_memory until cv_hmm_destroy), 10^x to within 2 ulp; entries below 10^-300 are
+ * outside the accuracy contract (they underflow gradually).  Every step rescales its row by
+ * an exact power of two, so |loglik - exact| <= 2 T (N + 8) u / ln 10 + 4 T u max(1, S) and
+ * |gamma - exact| <= 4 T (N + 8) u gamma + 1e-290 with u = 2^-53 (Posterior).
+ * Results are bit-identical between two calls and between the two variants.
+ * cv_last_timing: fwd_ms the forward pass, bt_ms the backward pass, kernel CV_KERNEL_AUTO (the
+ * matrix-core kernel; mfma_tiles = its 32 sequences per workgroup) or CV_KERNEL_GENERIC,
+ * padded_states NP.  Host pointers; synchronous. */
+CV_API cv_status cv_posterior_batch(cv_hmm* h, int64_t nseq, const int64_t* offsets, const int32_t* obs,
+                                    const cv_opts* opts, double* loglik_out, int32_t* path_out,
+                                    double* gamma_out, uint8_t* status_out);
+/* The same on device-resident buffers, with cv_decode_batch_device's contract: enqueued on
+ * opts->stream (or the handle's stream), returns after enqueueing (so it reports CV_OK where
+ * the host variant reports CV_EINFEASIBLE: read status_dev); offsets_host (nullable) is a host
+ * copy of the offsets; opts->forced is a device pointer. */
+CV_API cv_status cv_posterior_batch_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
+                                           const int64_t* offsets_dev, const int32_t* obs_dev, const cv_opts* opts,
+                                           double* loglik_dev, int32_t* path_dev, double* gamma_dev,
+                                           uint8_t* status_dev);
 
 /* ---- trait Solver (viterbi_solver.rs:11-16) -------------------------------------------
  * kind: "gpu"      f32 trellis kernel, VITERBI association, f64 re-scored objective
