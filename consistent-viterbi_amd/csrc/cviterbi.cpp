@@ -35,6 +35,7 @@
 #include "kernels/cfn.h"
 #include "kernels/exact.h"
 #include "kernels/fit.h"
+#include "kernels/kbest.h"
 #include "kernels/posterior.h"
 #include "kernels/trellis.h"
 #include "kernels/trellis64.h"
@@ -258,6 +259,10 @@ struct cv_hmm {
   // host API's gamma staging
   DevBuf ps_rows, ps_order, st_gamma;
   OrderStage ps_pin;
+  // K-best workspace: the u16 back-pointers of one chunk, each sequence's last lists, the
+  // longest-first order, the ranks' end points, and the host API's count staging
+  DevBuf kb_bp, kb_last, kb_order, kb_end, st_count;
+  OrderStage kb_pin;
   // workspace
   DevBuf ws_main, ws_last, ws_order;
   // a second decode workspace + stream: the constrained decode's unconstrained sequences run
@@ -1445,6 +1450,152 @@ cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
   return CV_OK;
 }
 
+// ---- K-best (list) Viterbi: cv_kbest_batch* ---------------------------------------------------
+// Core of cv_kbest_batch*: all pointers are device pointers except offsets_host.  Chunks of whole
+// sequences (original order) whose u16 back-pointers (N * KT * 2 bytes per element) fit the
+// workspace cap run forward, select and walk on `stream`.
+cv_status kbest_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, const int64_t* offsets_dev,
+                       const int32_t* obs_dev, int32_t k, const cv_opts& o, int32_t* path_dev, double* score_dev,
+                       int32_t* count_dev, uint8_t* status_dev, hipStream_t stream) {
+  if (o.dtype == CV_DTYPE_F32) return set_err(CV_EUNSUPPORTED, "the K-best path is f64 only");
+  if (o.dtype != CV_DTYPE_F64) return set_err(CV_EINVAL, "bad dtype %d", o.dtype);
+  if (o.assoc != CV_ASSOC_VITERBI)
+    return set_err(CV_EINVAL, "the K-best path covers the VITERBI association only (assoc %d)", o.assoc);
+  if (o.kernel != CV_KERNEL_AUTO && o.kernel != CV_KERNEL_GENERIC)
+    return set_err(CV_EINVAL, "K-best kernel must be AUTO or GENERIC (kernel %d)", o.kernel);
+  if (k < 1 || k > cvkb::kKbestMaxK) return set_err(CV_EINVAL, "k = %d outside [1, %d]", k, cvkb::kKbestMaxK);
+  const int N = h->N, KT = cvkb::kbest_width(k);
+  if (N > cvkb::kKbestMaxStates)
+    return set_err(CV_EUNSUPPORTED, "the K-best kernels cover N <= %d (N=%d)", cvkb::kKbestMaxStates, N);
+  if (N * KT > cvkb::kKbestMaxCells)
+    return set_err(CV_EUNSUPPORTED, "the K-best kernels cover N * KT <= %d (N=%d, k=%d: list width KT=%d)",
+                   cvkb::kKbestMaxCells, N, k, KT);
+  std::vector<int64_t> off_copy;
+  if (!offsets_host) {
+    off_copy.resize((size_t)nseq + 1);
+    HIP_TRY(hipMemcpyAsync(off_copy.data(), offsets_dev, off_copy.size() * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    offsets_host = off_copy.data();
+  }
+  cv_status st = check_batch(h, nseq, offsets_host);
+  if (st != CV_OK) return st;
+  if ((st = ensure_f64_tables(h)) != CV_OK) return st;
+  const int S = cvkb::kbest_seqs_per_wg(N, KT, nseq);
+  h->last_launches = 0;
+  h->last_kernel = CV_KERNEL_GENERIC;
+  h->last_np = KT;
+  h->last_mt = S;
+  if (nseq == 0) return CV_OK;
+  if (h->ws_rec) HIP_TRY(hipStreamWaitEvent(stream, h->ws_done, 0));
+  HIP_TRY(hipMemsetAsync(status_dev, 0, (size_t)nseq, stream));
+
+  const uint64_t per_elem = (uint64_t)N * KT * 2;
+  const uint64_t cap = o.workspace_bytes ? o.workspace_bytes : default_workspace_cap(h->kb_bp.bytes, kDefaultWorkspace);
+  const uint64_t elem_cap = cap / per_elem;
+  for (int64_t s = 0; s < nseq; ++s) {
+    const uint64_t T = (uint64_t)(offsets_host[s + 1] - offsets_host[s]);
+    if (T > elem_cap)
+      return set_err(CV_ENOMEM, "sequence %lld needs %llu bytes of back-pointers (T=%llu, N=%d, KT=%d), workspace cap %llu",
+                     (long long)s, (unsigned long long)(T * per_elem), (unsigned long long)T, N, KT,
+                     (unsigned long long)cap);
+  }
+  std::vector<std::pair<int64_t, int64_t>> chunks;
+  uint64_t max_elems = 0;
+  int64_t max_seqs = 0;
+  {
+    // equal shares rather than full chunks and a remainder: every launch fills the device alike
+    const uint64_t total_elems = (uint64_t)(offsets_host[nseq] - offsets_host[0]);
+    const uint64_t nchunks = std::max<uint64_t>(1, (total_elems + elem_cap - 1) / std::max<uint64_t>(elem_cap, 1));
+    const uint64_t target = std::max<uint64_t>(1, (total_elems + nchunks - 1) / nchunks);
+    for (int64_t s0 = 0; s0 < nseq;) {
+      int64_t s1 = s0;
+      uint64_t elems = 0;
+      while (s1 < nseq && s1 - s0 < (1 << 30)) {
+        const uint64_t T = (uint64_t)(offsets_host[s1 + 1] - offsets_host[s1]);
+        if (s1 > s0 && (elems + T > elem_cap || elems + T > target)) break;
+        elems += T;
+        ++s1;
+      }
+      max_elems = std::max(max_elems, elems);
+      max_seqs = std::max(max_seqs, s1 - s0);
+      chunks.emplace_back(s0, s1);
+      s0 = s1;
+    }
+  }
+  if ((st = h->kb_bp.ensure((size_t)std::max<uint64_t>(max_elems, 1) * per_elem)) != CV_OK) return st;
+  if ((st = h->kb_last.ensure((size_t)max_seqs * N * KT * 8)) != CV_OK) return st;
+  if ((st = h->kb_end.ensure((size_t)nseq * k * 4)) != CV_OK) return st;
+  // longest first inside each chunk (stable), so a workgroup's sequences have similar lengths
+  const int32_t* order_dev = nullptr;
+  bool varlen = false;
+  const int64_t T0 = offsets_host[1] - offsets_host[0];
+  for (int64_t s = 1; s < nseq && !varlen; ++s) varlen = (offsets_host[s + 1] - offsets_host[s]) != T0;
+  if (varlen) {
+    if (nseq > INT32_MAX) return set_err(CV_EINVAL, "too many sequences (%lld)", (long long)nseq);
+    std::vector<int32_t>& ord = h->order_host;
+    ord.resize((size_t)nseq);
+    std::iota(ord.begin(), ord.end(), 0);
+    auto len = [&](int32_t x) { return offsets_host[x + 1] - offsets_host[x]; };
+    for (const auto& c : chunks)
+      std::stable_sort(ord.begin() + c.first, ord.begin() + c.second, [&](int32_t x, int32_t y) { return len(x) > len(y); });
+    if ((st = h->kb_order.ensure((size_t)nseq * 4)) != CV_OK) return st;
+    int32_t* pin = h->kb_pin.acquire((size_t)nseq);
+    if (!pin) return set_err(CV_ENOMEM, "pinned staging of %lld order entries failed", (long long)nseq);
+    std::memcpy(pin, ord.data(), (size_t)nseq * 4);
+    HIP_TRY(hipMemcpyAsync(h->kb_order.p, pin, (size_t)nseq * 4, hipMemcpyHostToDevice, stream));
+    HIP_TRY(h->kb_pin.release(stream));
+    order_dev = h->kb_order.as<int32_t>();
+  }
+  const size_t nev = 4 * chunks.size();
+  if (h->acc_on && h->acc_used + nev > kMaxTimedEvents) h->acc_on = false, h->acc_overflow = true;
+  const size_t eb = h->acc_on ? h->acc_used : 0;
+  h->last_ev_base = eb;
+  for (size_t i = 0; i < nev; ++i)
+    if (!get_event(h->ev, eb + i)) return set_err(CV_EDEVICE, "hipEventCreate failed");
+  for (size_t ci = 0; ci < chunks.size(); ++ci) {
+    const auto& c = chunks[ci];
+    cvkb::KbestArgs g{};
+    g.pi = h->d_pi64.as<double>();
+    g.a = h->d_a64.as<double>();
+    g.et = h->d_et64.as<double>();
+    g.offsets = offsets_dev;
+    g.obs = obs_dev;
+    g.forced = o.forced;
+    g.order = order_dev;
+    g.seq_begin = c.first;
+    g.seq_end = c.second;
+    g.elem_base = offsets_host[c.first];
+    g.nstates = N;
+    g.nobs = (int)h->V;
+    g.k = k;
+    g.kt = KT;
+    g.bp = h->kb_bp.as<uint16_t>();
+    g.last = h->kb_last.as<double>();
+    g.end = h->kb_end.as<int32_t>();
+    g.plane = offsets_host[nseq];
+    g.path = path_dev;
+    g.score = score_dev;
+    g.count = count_dev;
+    g.status = status_dev;
+    hipEvent_t f0 = h->ev[eb + 4 * ci], f1 = h->ev[eb + 4 * ci + 1], b0 = h->ev[eb + 4 * ci + 2], b1 = h->ev[eb + 4 * ci + 3];
+    HIP_TRY(hipEventRecord(f0, stream));
+    hipError_t err = cvkb::launch_kbest_fwd(g, S, stream);
+    if (err != hipSuccess) return set_err(CV_EDEVICE, "K-best forward launch failed: %s", hipGetErrorString(err));
+    HIP_TRY(hipEventRecord(f1, stream));
+    HIP_TRY(hipEventRecord(b0, stream));
+    err = cvkb::launch_kbest_select(g, stream);
+    if (err == hipSuccess) err = cvkb::launch_kbest_walk(g, stream);
+    if (err != hipSuccess) return set_err(CV_EDEVICE, "K-best select / walk launch failed: %s", hipGetErrorString(err));
+    HIP_TRY(hipEventRecord(b1, stream));
+    h->last_launches = (int64_t)ci + 1;
+  }
+  if (h->acc_on) h->acc_used += nev;
+  if (!h->ws_done) HIP_TRY(hipEventCreateWithFlags(&h->ws_done, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(h->ws_done, stream));
+  h->ws_rec = true;
+  return CV_OK;
+}
+
 cv_opts default_opts() {
   cv_opts o;
   cv_opts_init(&o);
@@ -1544,7 +1695,7 @@ CV_API cv_status cv_hmm_release_workspaces(cv_hmm* h) {
                     &h->chainb.q, &h->chainb.ends, &h->chainb.gid, &h->chainb.gpath, &h->chainb.first,
                     &h->chainb.rpsi, &h->chainb.rows, &h->chainb.small, &h->chainb.rpath, &h->chainb.soff,
                     &h->chainb.sobs, &h->chainb.spath, &h->chainb.sres, &h->chainb.sinit, &h->chainb.slast, &h->ps_rows,
-                    &h->ps_order, &h->st_gamma})
+                    &h->ps_order, &h->st_gamma, &h->kb_bp, &h->kb_last, &h->kb_order, &h->kb_end, &h->st_count})
     b->release();
   h->ws_rec = false;
   h->side.ws_rec = false;
@@ -1766,6 +1917,82 @@ CV_API cv_status cv_posterior_batch(cv_hmm* h, int64_t nseq, const int64_t* offs
   for (int64_t s = 0; s < nseq; ++s)
     if (status_out[s] == CV_SEQ_INFEASIBLE)
       return set_err(CV_EINFEASIBLE, "sequence %lld has likelihood 0", (long long)s);
+  return CV_OK;
+}
+
+CV_API cv_status cv_kbest_batch_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
+                                       const int64_t* offsets_dev, const int32_t* obs_dev, int32_t k,
+                                       const cv_opts* opts, int32_t* path_dev, double* score_dev,
+                                       int32_t* count_dev, uint8_t* status_dev) {
+  if (!h) return set_err(CV_EINVAL, "null handle");
+  if (nseq < 0) return set_err(CV_EINVAL, "nseq < 0");
+  if (k < 1 || k > cvkb::kKbestMaxK) return set_err(CV_EINVAL, "k = %d outside [1, %d]", k, cvkb::kKbestMaxK);
+  if (nseq > 0 && (!offsets_dev || !obs_dev || !path_dev || !score_dev || !count_dev || !status_dev))
+    return set_err(CV_EINVAL, "null device buffer");
+  CV_LOCK(h);
+  cv_status st = set_device(h);
+  if (st != CV_OK) return st;
+  const cv_opts o = opts ? *opts : default_opts();
+  hipStream_t stream = o.stream ? (hipStream_t)o.stream : h->stream;
+  return kbest_device(h, nseq, offsets_host, offsets_dev, obs_dev, k, o, path_dev, score_dev, count_dev, status_dev,
+                      stream);
+}
+
+CV_API cv_status cv_kbest_batch(cv_hmm* h, int64_t nseq, const int64_t* offsets, const int32_t* obs, int32_t k,
+                                const cv_opts* opts, int32_t* path_out, double* score_out, int32_t* count_out,
+                                uint8_t* status_out) {
+  if (!h) return set_err(CV_EINVAL, "null handle");
+  if (k < 1 || k > cvkb::kKbestMaxK) return set_err(CV_EINVAL, "k = %d outside [1, %d]", k, cvkb::kKbestMaxK);
+  if (nseq < 0 || (nseq > 0 && (!offsets || !obs || !path_out || !score_out || !count_out || !status_out)))
+    return set_err(CV_EINVAL, "null argument");
+  CV_LOCK(h);
+  cv_status st = set_device(h);
+  if (st != CV_OK) return st;
+  cv_opts o = opts ? *opts : default_opts();
+  if (nseq == 0) return CV_OK;
+  if ((st = check_batch(h, nseq, offsets)) != CV_OK) return st;
+  const int64_t base = offsets[0], total = offsets[nseq];
+  const int64_t N = h->N;
+  const size_t plane = (size_t)std::max<int64_t>(total, 1);
+  hipStream_t stream = o.stream ? (hipStream_t)o.stream : h->stream;
+  if ((st = h->st_off.ensure((size_t)(nseq + 1) * 8)) != CV_OK) return st;
+  if ((st = h->st_obs.ensure(plane * 4)) != CV_OK) return st;
+  if ((st = h->st_path.ensure(plane * (size_t)k * 4)) != CV_OK) return st;
+  if ((st = h->st_score.ensure((size_t)nseq * k * 8)) != CV_OK) return st;
+  if ((st = h->st_count.ensure((size_t)nseq * 4)) != CV_OK) return st;
+  if ((st = h->st_status.ensure((size_t)nseq)) != CV_OK) return st;
+  HIP_TRY(hipMemcpyAsync(h->st_off.p, offsets, (size_t)(nseq + 1) * 8, hipMemcpyHostToDevice, stream));
+  // the observations are range-checked on the device (CV_SEQ_BADOBS), as in the _device variant
+  if (total > base)
+    HIP_TRY(hipMemcpyAsync(h->st_obs.as<int32_t>() + base, obs + base, (size_t)(total - base) * 4,
+                           hipMemcpyHostToDevice, stream));
+  if (o.forced) {
+    const int32_t* fr = o.forced;
+    const int64_t kb = first_bad(base, total, [&](int64_t i) { return fr[i] < -1 || fr[i] >= N; });
+    if (kb >= 0) return set_err(CV_EINVAL, "forced[%lld] = %d out of range [-1,%d)", (long long)kb, fr[kb], h->N);
+    if ((st = h->st_forced.ensure(plane * 4)) != CV_OK) return st;
+    if (total > base)
+      HIP_TRY(hipMemcpyAsync(h->st_forced.as<int32_t>() + base, fr + base, (size_t)(total - base) * 4,
+                             hipMemcpyHostToDevice, stream));
+    o.forced = h->st_forced.as<int32_t>();
+  }
+  st = kbest_device(h, nseq, offsets, h->st_off.as<int64_t>(), h->st_obs.as<int32_t>(), k, o, h->st_path.as<int32_t>(),
+                    h->st_score.as<double>(), h->st_count.as<int32_t>(), h->st_status.as<uint8_t>(), stream);
+  if (st != CV_OK) {
+    (void)hipStreamSynchronize(stream);
+    return st;
+  }
+  if (total > base)
+    for (int32_t r = 0; r < k; ++r)  // plane r of the staging and of path_out: offsets[nseq] elements each
+      HIP_TRY(hipMemcpyAsync(path_out + (size_t)r * total + base, h->st_path.as<int32_t>() + (size_t)r * total + base,
+                             (size_t)(total - base) * 4, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(score_out, h->st_score.p, (size_t)nseq * k * 8, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(count_out, h->st_count.p, (size_t)nseq * 4, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(status_out, h->st_status.p, (size_t)nseq, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  for (int64_t s = 0; s < nseq; ++s)
+    if (status_out[s] == CV_SEQ_INFEASIBLE)
+      return set_err(CV_EINFEASIBLE, "sequence %lld has no path of finite score", (long long)s);
   return CV_OK;
 }
 

@@ -43,6 +43,7 @@ EXPORTS = [
     "cv_hmm_fit_mle", "cv_hmm_fit_train", "cv_solver_write_cfn",
     "cv_hmm_set_tuning", "cv_hmm_get_tuning", "cv_tuning_key", "cv_hmm_release_workspaces",
     "cv_posterior_batch", "cv_posterior_batch_device",
+    "cv_kbest_batch", "cv_kbest_batch_device",
 ]
 
 
@@ -122,6 +123,8 @@ def lib():
         "cv_decode_batch_device": ([P, I64, P, P, P, P, P, P, P], S),
         "cv_posterior_batch": ([P, I64, P, P, P, P, P, P, P], S),
         "cv_posterior_batch_device": ([P, I64, P, P, P, P, P, P, P, P], S),
+        "cv_kbest_batch": ([P, I64, P, P, I32, P, P, P, P, P], S),
+        "cv_kbest_batch_device": ([P, I64, P, P, P, I32, P, P, P, P, P], S),
         "cv_last_timing": ([P, P], S),
         "cv_timing_begin": ([P], S),
         "cv_timing_end": ([P, P], S),

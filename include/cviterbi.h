@@ -211,7 +211,7 @@ CV_API void cv_hmm_destroy(cv_hmm* h);
  *                         per-sequence E-step kernels / the xi GEMM path at every N
  * Unknown keys and values outside int32 are CV_EINVAL.  cv_tuning_key(i) lists the keys
  * (NULL past the last). */
-/* Frees the handle's decode workspaces (delta rows, the posterior path's forward rows, the
+/* Frees the handle's decode workspaces (delta rows, the posterior path's forward rows, the K-best back-pointers and last lists, the
  * constrained decode's and the parallel chain's per-call buffers, pinned staging), which are otherwise kept grow-only between calls
  * so repeated calls do not reallocate: e.g. ~1 GB of chain buffers (observations, paths, the
  * speculative batches' psi rows) and 18 MiB of pinned staging plus the 34-69 GB delta workspace
@@ -421,6 +421,59 @@ CV_API cv_status cv_posterior_batch_device(cv_hmm* h, int64_t nseq, const int64_
                                            const int64_t* offsets_dev, const int32_t* obs_dev, const cv_opts* opts,
                                            double* loglik_dev, int32_t* path_dev, double* gamma_dev,
                                            uint8_t* status_dev);
+
+/* ---- K-best (list) Viterbi decoding, exact f64 --------------------------------------------
+ * The k best paths of every sequence under the row-A0 (VITERBI) association in f64, with their
+ * scores.  The score of a path s is the reference's fold along it:
+ *   d = pi[s_0] + b[s_0, o_0], then d = (d + a[s_t-1, s_t]) + b[s_t, o_t];
+ * a path whose score is -inf is not a path.  fl(x + c) is monotone in x, so the K best lists of
+ * the predecessors determine the K best list of a state and the recurrence is well defined:
+ *   L_0(j) = [pi[j] + b[j, o_0]] if finite, else empty;
+ *   t >= 1: the candidates of state j are x(i, r) = L_t-1(i)[r] + a[i, j] over all states i and
+ *     ranks r; L_t(j) is the first K FINITE candidates in the order value descending, ties by
+ *     (i, r) ascending (a stable descending sort of the candidates laid out at index i * K + r);
+ *     b[j, o_t] is then added to each -- the order is fixed before the emission is added -- and
+ *     a -inf emission empties the list;
+ *   result: the entries L_T-1(j)[r] in the order value descending, ties by (j, r) ascending;
+ *     the first K are ranks 0 .. K-1, each followed back through its (i, r) back-pointers.
+ * A forced element (opts->forced, as in cv_decode_batch) admits only its state: every other
+ * list at that element is empty.  Consequences: rank 0 is cv_decode_batch's f64 VITERBI path
+ * and score, bit for bit, for every feasible sequence; every reported score is the f64 fold
+ * along its reported path; the first K' ranks of a K-best call are the K'-best call's result.
+ * Outputs, with L = offsets[nseq]: path_out is rank-major, plane r (path_out + r * L) a whole
+ * path array in cv_decode_batch's layout; score_out[s * k + r]; count_out[s] = min(k, number of
+ * finite-score paths of sequence s).  Ranks count_out[s] .. k-1 are unused: score -inf, path -1.
+ * status_out: CV_SEQ_OK (count >= 1); CV_SEQ_INFEASIBLE (count 0, every rank unused);
+ * CV_SEQ_EMPTY (empty sequence: count 0, scores -inf); CV_SEQ_BADOBS (an observation outside
+ * [0, V), checked on the device by both variants: count 0, paths -1, scores NaN).  No sequence
+ * disturbs another.  The host variant returns CV_EINFEASIBLE, after writing every output, when
+ * a sequence is infeasible.
+ * opts: dtype CV_DTYPE_F64 (CV_DTYPE_F32 is CV_EUNSUPPORTED); assoc CV_ASSOC_VITERBI (others
+ * CV_EINVAL); kernel CV_KERNEL_AUTO or CV_KERNEL_GENERIC (the same kernels; CV_KERNEL_TRELLIS*
+ * is CV_EINVAL); forced, stream and workspace_bytes are honoured.  Limits: 1 <= k <= 16 (else
+ * CV_EINVAL); N <= 1,024 and N * KT <= 8,192 (else CV_EUNSUPPORTED), KT = k rounded up to the
+ * kernels' list width 2, 4, 8 or 16 (two list rows of N * KT f64 in 128 KiB of LDS).
+ * Workspace: u16 back-pointers (i << 4 | r) per (element, state, rank), N * KT * 2 bytes per
+ * element, in the handle's workspace, in chunks of whole sequences under opts->workspace_bytes
+ * (0 = the generic kernels' default, 8 GiB); a single sequence over the cap is CV_ENOMEM.  The
+ * last lists (N * KT * 8 bytes per sequence of a chunk) are kept beside them;
+ * cv_hmm_release_workspaces frees both.
+ * cv_last_timing: fwd_ms the forward pass, bt_ms select plus walk, launches the chunks, kernel
+ * CV_KERNEL_GENERIC, padded_states KT, mfma_tiles the sequences per forward workgroup (1, 2 or
+ * 4).  Results are bit-identical between two calls and between the two variants.
+ * Host pointers; synchronous. */
+CV_API cv_status cv_kbest_batch(cv_hmm* h, int64_t nseq, const int64_t* offsets, const int32_t* obs,
+                                int32_t k, const cv_opts* opts, int32_t* path_out /*[k][L]*/,
+                                double* score_out /*[nseq][k]*/, int32_t* count_out /*[nseq]*/,
+                                uint8_t* status_out /*[nseq]*/);
+/* The same on device-resident buffers, with cv_posterior_batch_device's contract: enqueued on
+ * opts->stream (or the handle's stream), returns after enqueueing (so it reports CV_OK where
+ * the host variant reports CV_EINFEASIBLE: read status_dev); offsets_host (nullable) is a host
+ * copy of the offsets; opts->forced is a device pointer. */
+CV_API cv_status cv_kbest_batch_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
+                                       const int64_t* offsets_dev, const int32_t* obs_dev, int32_t k,
+                                       const cv_opts* opts, int32_t* path_dev, double* score_dev,
+                                       int32_t* count_dev, uint8_t* status_dev);
 
 /* ---- trait Solver (viterbi_solver.rs:11-16) -------------------------------------------
  * kind: "gpu"      f32 trellis kernel, VITERBI association, f64 re-scored objective
