@@ -35,6 +35,7 @@
 #include "kernels/cfn.h"
 #include "kernels/exact.h"
 #include "kernels/fit.h"
+#include "kernels/emis.h"
 #include "kernels/kbest.h"
 #include "kernels/posterior.h"
 #include "kernels/trellis.h"
@@ -280,6 +281,7 @@ struct cv_hmm {
     hipEvent_t start = nullptr, done = nullptr, after = nullptr;
   } side;
   DevBuf st_off, st_obs, st_path, st_score, st_status, st_forced;
+  DevBuf st_emis;  // cv_decode_emissions: the host array's rows, compact ([elements][N])
   DevBuf cs_ranges, cs_delta, cs_g, cs_mu, cs_start, cs_zero, cs_queue;  // constrained-decode scratch
   DevBuf cs_wrows;  // the wide generic_ext's rows ([slot][2][N], N > 10,240)
   DevBuf cs_comp, cs_words;  // device exact unary sums: per-sequence components, output words
@@ -334,6 +336,7 @@ struct cv_hmm {
   // the parallel chain's path copy: per decode chunk, behind that chunk's backtrack (chunk_ev),
   // on a non-blocking stream of its own, from a host thread of its own
   std::vector<hipEvent_t> chunk_ev;
+  std::vector<hipEvent_t> emis_ev;  // dense emissions: chunk k's rows staged (on bt_stream, beside chunk k-1)
   hipStream_t copy_stream = nullptr;
   PinnedHost chain_pin;  // the chain's scores, statuses and certificates on their way to the host
   PinnedHost chain_gpin;  // the chain's gathered candidate paths and speculative results (16 MiB)
@@ -359,6 +362,7 @@ struct cv_hmm {
     if (stream) (void)hipStreamDestroy(stream);
     if (bt_stream) (void)hipStreamDestroy(bt_stream);
     for (auto e : chunk_ev) (void)hipEventDestroy(e);
+    for (auto e : emis_ev) (void)hipEventDestroy(e);
     for (auto e : part_ev) (void)hipEventDestroy(e);
     if (copy_stream) (void)hipStreamDestroy(copy_stream);
     if (chain_stream) (void)hipStreamDestroy(chain_stream);
@@ -712,13 +716,64 @@ cvk::BacktrackArgs make_bt_args(cv_hmm* h, unsigned char* wsb, const int64_t* of
   return ba;
 }
 
+// Caller-supplied emission scores (cv_decode_emissions*): a dense device array, row e (element
+// index of the CSR offsets) at p + e * ld, N log10 scores each.
+struct EmisSrc {
+  const double* p;
+  int64_t ld;
+};
+
+// What a decode kernel reads its emissions through: row et + obs[e] * stride, obs[e] < nobs.
+struct EmisView {
+  const double* et;
+  const int32_t* obs;
+  int nobs;
+};
+
+// Stages the dense rows of the chunk of sequences c (elements [e0, e1)) at the table stride of
+// the kernel that will decode them and returns that kernel's (et, obs, nobs): et = the staged
+// rows, obs[e] = e - e0 for the chunk's elements, nobs = e1 - e0.  `staged` ([e1 - e0][stride]
+// f64, 16-byte aligned) and `idx` ([e1 - e0] int32) must live until the chunk's backtrack has
+// run.  emis_prepare_f64 (emis.hip) runs on `stream`; a NaN or +inf sets status BADOBS.
+cv_status stage_emissions(const cv_hmm* h, const EmisSrc& src, const int64_t* offsets_host,
+                          const int64_t* offsets_dev, const std::pair<int64_t, int64_t>& c, int stride,
+                          double* staged, int32_t* idx, uint8_t* status_dev, hipStream_t stream, EmisView* out) {
+  const int64_t e0 = offsets_host[c.first], e1 = offsets_host[c.second];
+  if (e1 - e0 > INT32_MAX) return set_err(CV_ELIMIT, "chunk of %lld elements of dense emissions", (long long)(e1 - e0));
+  cvem::EmisPrepArgs g{};
+  g.src = src.p;
+  g.ld = src.ld;
+  g.e0 = e0;
+  g.nrows = e1 - e0;
+  g.nstates = h->N;
+  g.stride = stride;
+  g.dst = staged;
+  g.idx = idx;
+  g.offsets = offsets_dev;
+  g.seq_begin = c.first;
+  g.seq_end = c.second;
+  g.status = status_dev;
+  const hipError_t err = cvem::launch_emis_prepare(g, h->cus, stream);
+  if (err != hipSuccess) return set_err(CV_EDEVICE, "emission staging launch failed: %s", hipGetErrorString(err));
+  out->et = staged;
+  // the kernels index obs by absolute element: (idx - e0)[e] = idx[e - e0]
+  out->obs = reinterpret_cast<const int32_t*>(reinterpret_cast<uintptr_t>(idx) - (uintptr_t)e0 * 4);
+  out->nobs = (int)(e1 - e0);
+  return CV_OK;
+}
+
 // Core device-side decode.  All pointers are device pointers except offsets_host.
+// emis (cv_decode_emissions*, f64 only): the emissions of every element come from this dense
+// array instead of the handle's b through obs_dev (ignored, may be null): each chunk's rows are
+// staged beside its delta rows (stage_emissions) and the same kernels decode them; the caller
+// has checked the options (emissions_opts_ok: f64, not the f32 trellis kernel).
 cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, const int64_t* offsets_dev,
                         const int32_t* obs_dev, const cv_opts& o, int32_t* path_dev, double* score_dev,
                         uint8_t* status_dev, hipStream_t stream, const void* resume_rows = nullptr,
                         bool side_ws = false, double* cp_cert = nullptr, const double* cp_init = nullptr,
                         double* cp_last = nullptr,
-                        std::vector<std::pair<int64_t, int64_t>>* chunks_out = nullptr) {
+                        std::vector<std::pair<int64_t, int64_t>>* chunks_out = nullptr,
+                        const EmisSrc* emis = nullptr) {
   // cp_cert (the parallel CPSolver chain, row-A0 f64 trellis only): each chunk's backtrack
   // computes its certificates (or cp_cert_f64 reads the chunk's rows and paths) -> [nseq][2];
   // chunks_out: h->chunk_ev[i] is recorded after chunk i's backtrack (its paths written,
@@ -845,6 +900,11 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
                            : gen_rows ? (uint64_t)h->N * (o.dtype == CV_DTYPE_F64 ? 8 : 4)
                                        : (uint64_t)h->N * 2;
   const int real_bytes = o.dtype == CV_DTYPE_F64 ? 8 : 4;
+  // dense emissions: a chunk's staged rows [elements][estride] f64 and its index array follow
+  // its delta rows in the same buffer, so the cap covers them and they live as long
+  const int estride = use_t64 ? h->np64 : h->N;
+  const uint64_t rows_per_elem = per_elem;
+  const uint64_t stage_per_elem = emis ? (uint64_t)estride * 8 + 4 : 0;
   const uint64_t total_elems = (uint64_t)(offsets_host[nseq] - offsets_host[0]);
   // Chunks (contiguous in the original order) are pipelined over two streams: the forward
   // pass of chunk k+1 runs while chunk k backtracks, out of a double-buffered workspace.
@@ -862,44 +922,58 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
     const int v = h->tuning.max_chunks;
     return (uint64_t)(v >= 1 && v <= 64 ? v : 8);
   }();
-  const uint64_t half_cap = std::max<uint64_t>(serial ? cap : cap / 2, per_elem);
-  uint64_t nchunks = std::max<uint64_t>(1, (total_elems * per_elem + half_cap - 1) / half_cap);
-  if (!serial) nchunks = std::max<uint64_t>(nchunks, std::min<uint64_t>(max_chunks, (uint64_t)(nseq / 2048)));
-  const uint64_t target = std::max<uint64_t>(1, (total_elems + nchunks - 1) / nchunks);
-  const uint64_t elem_cap = std::max<uint64_t>(half_cap / per_elem, 1);
   std::vector<std::pair<int64_t, int64_t>> chunks;
-  {
-    int64_t s0 = 0;
-    while (s0 < nseq) {
-      int64_t s1 = s0;
-      uint64_t elems = 0;
-      while (s1 < nseq) {
-        const uint64_t T = (uint64_t)(offsets_host[s1 + 1] - offsets_host[s1]);
-        if (s1 > s0 && (elems + T > elem_cap || elems + T > target)) break;
-        elems += T;
-        ++s1;
-        if (s1 - s0 >= (1 << 30)) break;
+  // the batch split under the cap at per_elem_all workspace bytes per element
+  auto split = [&](const uint64_t per_elem_all) {
+    chunks.clear();
+    const uint64_t half_cap = std::max<uint64_t>(serial ? cap : cap / 2, per_elem_all);
+    uint64_t nchunks = std::max<uint64_t>(1, (total_elems * per_elem_all + half_cap - 1) / half_cap);
+    if (!serial) nchunks = std::max<uint64_t>(nchunks, std::min<uint64_t>(max_chunks, (uint64_t)(nseq / 2048)));
+    const uint64_t target = std::max<uint64_t>(1, (total_elems + nchunks - 1) / nchunks);
+    const uint64_t elem_cap = std::max<uint64_t>(half_cap / per_elem_all, 1);
+    {
+      int64_t s0 = 0;
+      while (s0 < nseq) {
+        int64_t s1 = s0;
+        uint64_t elems = 0;
+        while (s1 < nseq) {
+          const uint64_t T = (uint64_t)(offsets_host[s1 + 1] - offsets_host[s1]);
+          if (s1 > s0 && (elems + T > elem_cap || elems + T > target)) break;
+          elems += T;
+          ++s1;
+          if (s1 - s0 >= (1 << 30)) break;
+        }
+        chunks.emplace_back(s0, s1);
+        s0 = s1;
       }
-      chunks.emplace_back(s0, s1);
-      s0 = s1;
     }
-  }
-  {
-    // Equal lengths: whole rounds of workgroups (group x CUs sequences) per chunk, so only
-    // the last chunk ends on a partly filled round (a chunk's launch waits for the last).
-    const int64_t T0c = offsets_host[1] - offsets_host[0];
-    bool uniform = T0c > 0;
-    for (int64_t s = 1; s < nseq && uniform; ++s) uniform = (offsets_host[s + 1] - offsets_host[s]) == T0c;
-    const int64_t unit = (use_t64 ? 64 : group) * (int64_t)std::max(h->cus, 1);
-    if (uniform && chunks.size() > 1) {
-      const int64_t cap_seqs = std::max<int64_t>((int64_t)(elem_cap / (uint64_t)T0c), 1);
-      int64_t per = (nseq + (int64_t)chunks.size() - 1) / (int64_t)chunks.size();
-      per = ((per + unit - 1) / unit) * unit;
-      if (per > cap_seqs) per = cap_seqs >= unit ? (cap_seqs / unit) * unit : cap_seqs;
-      chunks.clear();
-      for (int64_t s0 = 0; s0 < nseq; s0 += per) chunks.emplace_back(s0, std::min(nseq, s0 + per));
+    {
+      // Equal lengths: whole rounds of workgroups (group x CUs sequences) per chunk, so only
+      // the last chunk ends on a partly filled round (a chunk's launch waits for the last).
+      const int64_t T0c = offsets_host[1] - offsets_host[0];
+      bool uniform = T0c > 0;
+      for (int64_t s = 1; s < nseq && uniform; ++s) uniform = (offsets_host[s + 1] - offsets_host[s]) == T0c;
+      const int64_t unit = (use_t64 ? 64 : group) * (int64_t)std::max(h->cus, 1);
+      if (uniform && chunks.size() > 1) {
+        const int64_t cap_seqs = std::max<int64_t>((int64_t)(elem_cap / (uint64_t)T0c), 1);
+        int64_t per = (nseq + (int64_t)chunks.size() - 1) / (int64_t)chunks.size();
+        per = ((per + unit - 1) / unit) * unit;
+        if (per > cap_seqs) per = cap_seqs >= unit ? (cap_seqs / unit) * unit : cap_seqs;
+        chunks.clear();
+        for (int64_t s0 = 0; s0 < nseq; s0 += per) chunks.emplace_back(s0, std::min(nseq, s0 + per));
+      }
     }
-  }
+  };
+  split(rows_per_elem + stage_per_elem);
+  // Tuning key emis_overlap = 1 (bit-identical; off by default): dense emissions on the f64
+  // trellis (its chunks run back to back on one stream), more than one chunk: chunk k+1 is staged
+  // on the second stream beside chunk k's forward pass -- the staging is bound by bandwidth, the
+  // forward by the VALU -- into a SECOND staging buffer, so the batch is split again with 8P + 4
+  // bytes per element more under the same cap (a batch that fits one chunk is never split for
+  // it).  12,288 x 512 at N = 256: 2% faster at three chunks each, but under one cap the finer
+  // split decides: 57.0 vs 39.8 ms and 38.8 vs 49.3 ms at two caps (profiles/emissions_bench.txt)
+  const bool eov = emis && use_t64 && !side_ws && chunks.size() > 1 && h->tuning.emis_overlap != 0;
+  if (eov) split(rows_per_elem + 2 * stage_per_elem);
   uint64_t max_elems = 0;
   int64_t max_seqs = 0;
   bool varlen = false;
@@ -910,7 +984,21 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
   const int nbuf = (chunks.size() > 1 && !serial) ? 2 : 1;
   const int64_t T0 = offsets_host[1] - offsets_host[0];
   for (int64_t s = 1; s < nseq && !varlen; ++s) varlen = (offsets_host[s + 1] - offsets_host[s]) != T0;
-  const size_t buf_bytes = ((std::max<uint64_t>(max_elems, 1) * per_elem + 255) / 256) * 256;
+  const size_t rows_bytes = ((std::max<uint64_t>(max_elems, 1) * rows_per_elem + 255) / 256) * 256;
+  const size_t stage_bytes = emis ? ((std::max<uint64_t>(max_elems, 1) * estride * 8 + 255) / 256) * 256 : 0;
+  const size_t idx_bytes = emis ? ((std::max<uint64_t>(max_elems, 1) * 4 + 255) / 256) * 256 : 0;
+  const size_t buf_bytes = rows_bytes + (eov ? 2 : 1) * (stage_bytes + idx_bytes);
+  EmisView ev_next{};
+  // a staging pass enqueued on the second stream is joined by the forward pass of its chunk; if
+  // the call fails before that launch, it is waited for here, so no kernel of a failed call is
+  // left running on a stream the caller does not see
+  struct StageJoin {
+    hipStream_t s;
+    bool pending = false;
+    ~StageJoin() {
+      if (pending) (void)hipStreamSynchronize(s);
+    }
+  } stage_join{h->bt_stream};
   // gen_global: each sequence's two rows follow the chunk's last rows ([max_seqs][2][N])
   const size_t last_bytes = ((size_t)max_seqs * h->N * real_bytes * (gen_global ? 3 : 1) + 255) / 256 * 256;
   if ((st = w_main.ensure(buf_bytes * nbuf)) != CV_OK) return st;
@@ -994,6 +1082,7 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
     ba.obs = obs_dev;
     ba.et = h->q_et.as<double>();
     ba.at32 = h->t64_nonpos ? h->q_at32.as<float>() : nullptr;
+    if (emis) ba.at32 = nullptr;  // densities may be positive: the general f64 interval test
     return ba;
   };
   for (size_t ci = 0; ci < chunks.size(); ++ci) {
@@ -1005,6 +1094,19 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
     hipEvent_t f0 = evv[eb + 4 * ci], f1 = evv[eb + 4 * ci + 1], b0 = evv[eb + 4 * ci + 2], b1 = evv[eb + 4 * ci + 3];
     if (!serial && ci >= 2) HIP_TRY(hipStreamWaitEvent(stream, evv[eb + 4 * (ci - 2) + 3], 0));  // buffer reuse
     HIP_TRY(hipEventRecord(f0, stream));
+    EmisView ev{};  // dense emissions: this chunk's staged rows replace (table, obs_dev, V) below
+    auto stage = [&](size_t k, hipStream_t s, EmisView* out) {
+      unsigned char* sb = wsb + rows_bytes + (eov ? k % 2 : 0) * (stage_bytes + idx_bytes);
+      return stage_emissions(h, *emis, offsets_host, offsets_dev, chunks[k], estride, reinterpret_cast<double*>(sb),
+                             reinterpret_cast<int32_t*>(sb + stage_bytes), status_dev, s, out);
+    };
+    if (eov && ci > 0) {
+      HIP_TRY(hipStreamWaitEvent(stream, h->emis_ev[ci], 0));
+      stage_join.pending = false;
+      ev = ev_next;
+    } else if (emis && (st = stage(ci, stream, &ev)) != CV_OK) {
+      return st;
+    }
     hipError_t err;
     if (use_trellis) {
       cvk::TrellisFwdArgs fa{};
@@ -1055,6 +1157,7 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
       fa.dp_assoc = o.assoc == CV_ASSOC_DP ? 1 : 0;
       fa.forced = o.forced;
       fa.resume_rows = static_cast<const double*>(resume_rows);
+      if (emis) fa.et = ev.et, fa.obs = ev.obs, fa.nobs = ev.nobs;
       const int spw = cvk::t64_seqs_per_wave(n, h->cus, h->np64);
       // the S actually launched: CP / DP, NP = 1,024 and forced NP = 512 run S <= 4 (launch_t64_fwd)
       if (!side_ws)
@@ -1101,6 +1204,7 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
       fa.forced = o.forced;
       fa.cp_init = cp_init;  // the parallel chain's speculative re-decodes (N > 256)
       fa.cp_last = cp_last;
+      if (emis) fa.et = ev.et, fa.obs = ev.obs, fa.nobs = ev.nobs;
       if (gen_rows) fa.rows = reinterpret_cast<double*>(wsb);
       if (gen_global) {  // wide: the chunk's rows after its last rows, one launch per step
         fa.grows = reinterpret_cast<double*>(lrb) + (size_t)max_seqs * h->N;
@@ -1135,6 +1239,13 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
     }
     if (err != hipSuccess) return set_err(CV_EDEVICE, "forward launch failed: %s", hipGetErrorString(err));
     HIP_TRY(hipEventRecord(f1, stream));
+    if (eov && ci + 1 < chunks.size()) {  // chunk ci - 1 has finished with the other staging buffer at f0
+      if (!get_event(h->emis_ev, ci + 1)) return set_err(CV_EDEVICE, "hipEventCreate failed");
+      HIP_TRY(hipStreamWaitEvent(h->bt_stream, f0, 0));
+      stage_join.pending = true;
+      if ((st = stage(ci + 1, h->bt_stream, &ev_next)) != CV_OK) return st;
+      HIP_TRY(hipEventRecord(h->emis_ev[ci + 1], h->bt_stream));
+    }
     if (!serial) HIP_TRY(hipStreamWaitEvent(bts, f1, 0));
     HIP_TRY(hipEventRecord(b0, bts));
     if (use_trellis) {
@@ -1164,6 +1275,7 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
       }
     } else if (use_t64 && !t64cp) {
       cvk::T64BtArgs ba = t64_bt_args(c, wsb);
+      if (emis) ba.et = ev.et, ba.obs = ev.obs;
       // the parallel chain's certificates inside the backtrack (NONPOS row A0, NP <= 256): no
       // second pass over every row (tuning key chain_cert_fused = 0: the cp_cert_f64 pass)
       const bool fused_cert = cp_cert && ba.at32 && !ba.dp_assoc && !ba.decode_bt && h->np64 <= 256 &&
@@ -1220,6 +1332,7 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
         ba.assoc = o.assoc;
         ba.nobs = (int)h->V;
       }
+      if (emis) ba.et64 = ba.et = ev.et, ba.obs = ev.obs, ba.nobs = ev.nobs;
       err = gen_rows ? cvk::launch_generic_bt_rows<double>(ba, n, bts) : cvk::launch_generic_bt<double>(ba, n, bts);
       if (err == hipSuccess && chunks_out) {
         hipEvent_t ce = get_event(h->chunk_ev, chunks_out->size());
@@ -1695,7 +1808,8 @@ CV_API cv_status cv_hmm_release_workspaces(cv_hmm* h) {
                     &h->chainb.q, &h->chainb.ends, &h->chainb.gid, &h->chainb.gpath, &h->chainb.first,
                     &h->chainb.rpsi, &h->chainb.rows, &h->chainb.small, &h->chainb.rpath, &h->chainb.soff,
                     &h->chainb.sobs, &h->chainb.spath, &h->chainb.sres, &h->chainb.sinit, &h->chainb.slast, &h->ps_rows,
-                    &h->ps_order, &h->st_gamma, &h->kb_bp, &h->kb_last, &h->kb_order, &h->kb_end, &h->st_count})
+                    &h->ps_order, &h->st_gamma, &h->kb_bp, &h->kb_last, &h->kb_order, &h->kb_end, &h->st_count,
+                    &h->st_emis})
     b->release();
   h->ws_rec = false;
   h->side.ws_rec = false;
@@ -1993,6 +2107,92 @@ CV_API cv_status cv_kbest_batch(cv_hmm* h, int64_t nseq, const int64_t* offsets,
   for (int64_t s = 0; s < nseq; ++s)
     if (status_out[s] == CV_SEQ_INFEASIBLE)
       return set_err(CV_EINFEASIBLE, "sequence %lld has no path of finite score", (long long)s);
+  return CV_OK;
+}
+
+// ---- decode of caller-supplied emission scores: cv_decode_emissions* -------------------------
+static cv_status emissions_opts_ok(const cv_opts& o) {
+  if (o.dtype == CV_DTYPE_F32) return set_err(CV_EUNSUPPORTED, "dense emissions are decoded in f64 only");
+  if (o.dtype != CV_DTYPE_F64) return set_err(CV_EINVAL, "bad dtype %d", o.dtype);
+  if (o.kernel == CV_KERNEL_TRELLIS)
+    return set_err(CV_EUNSUPPORTED, "dense emissions: the f32 trellis kernel does not apply (AUTO, GENERIC or TRELLIS_F64)");
+  return CV_OK;
+}
+
+CV_API cv_status cv_decode_emissions_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
+                                            const int64_t* offsets_dev, const double* emis_dev, int64_t ld,
+                                            const cv_opts* opts, int32_t* path_dev, double* score_dev,
+                                            uint8_t* status_dev) {
+  if (!h) return set_err(CV_EINVAL, "null handle");
+  if (nseq < 0) return set_err(CV_EINVAL, "nseq < 0");
+  if (nseq > 0 && (!offsets_dev || !emis_dev || !path_dev || !score_dev || !status_dev))
+    return set_err(CV_EINVAL, "null device buffer");
+  if (ld < h->N) return set_err(CV_EINVAL, "ld = %lld is less than N = %d", (long long)ld, h->N);
+  const cv_opts o = opts ? *opts : default_opts();
+  cv_status st = emissions_opts_ok(o);
+  if (st != CV_OK) return st;
+  CV_LOCK(h);
+  if ((st = set_device(h)) != CV_OK) return st;
+  hipStream_t stream = o.stream ? (hipStream_t)o.stream : h->stream;
+  const EmisSrc src{emis_dev, ld};
+  return decode_device(h, nseq, offsets_host, offsets_dev, nullptr, o, path_dev, score_dev, status_dev, stream, nullptr,
+                       false, nullptr, nullptr, nullptr, nullptr, &src);
+}
+
+CV_API cv_status cv_decode_emissions(cv_hmm* h, int64_t nseq, const int64_t* offsets, const double* emis, int64_t ld,
+                                     const cv_opts* opts, int32_t* path_out, double* score_out, uint8_t* status_out) {
+  if (!h) return set_err(CV_EINVAL, "null handle");
+  if (nseq < 0 || (nseq > 0 && (!offsets || !emis || !path_out || !score_out || !status_out)))
+    return set_err(CV_EINVAL, "null argument");
+  if (ld < h->N) return set_err(CV_EINVAL, "ld = %lld is less than N = %d", (long long)ld, h->N);
+  cv_opts o = opts ? *opts : default_opts();
+  cv_status st = emissions_opts_ok(o);
+  if (st != CV_OK) return st;
+  CV_LOCK(h);
+  if ((st = set_device(h)) != CV_OK) return st;
+  if (nseq == 0) return CV_OK;
+  if ((st = check_batch(h, nseq, offsets)) != CV_OK) return st;
+  const int64_t base = offsets[0], total = offsets[nseq];
+  const int64_t N = h->N;
+  const size_t plane = (size_t)std::max<int64_t>(total, 1);
+  hipStream_t stream = o.stream ? (hipStream_t)o.stream : h->stream;
+  if ((st = h->st_off.ensure((size_t)(nseq + 1) * 8)) != CV_OK) return st;
+  if ((st = h->st_emis.ensure((size_t)std::max<int64_t>(total - base, 1) * N * 8)) != CV_OK) return st;
+  if ((st = h->st_path.ensure(plane * 4)) != CV_OK) return st;
+  if ((st = h->st_score.ensure((size_t)nseq * 8)) != CV_OK) return st;
+  if ((st = h->st_status.ensure((size_t)nseq)) != CV_OK) return st;
+  HIP_TRY(hipMemcpyAsync(h->st_off.p, offsets, (size_t)(nseq + 1) * 8, hipMemcpyHostToDevice, stream));
+  // the N scores of each row, compact on the device (the columns beyond N are never read)
+  if (total > base)
+    HIP_TRY(hipMemcpy2DAsync(h->st_emis.p, (size_t)N * 8, emis + base * ld, (size_t)ld * 8, (size_t)N * 8,
+                             (size_t)(total - base), hipMemcpyHostToDevice, stream));
+  if (o.forced) {  // host forced[] -> device staging, indexed like the elements
+    const int32_t* fr = o.forced;
+    const int64_t k = first_bad(base, total, [&](int64_t i) { return fr[i] < -1 || fr[i] >= N; });
+    if (k >= 0) return set_err(CV_EINVAL, "forced[%lld] = %d out of range [-1,%d)", (long long)k, fr[k], h->N);
+    if ((st = h->st_forced.ensure(plane * 4)) != CV_OK) return st;
+    if (total > base)
+      HIP_TRY(hipMemcpyAsync(h->st_forced.as<int32_t>() + base, fr + base, (size_t)(total - base) * 4,
+                             hipMemcpyHostToDevice, stream));
+    o.forced = h->st_forced.as<int32_t>();
+  }
+  // row e of the staging at p + e * N: the staging holds the elements from `base` on
+  const EmisSrc src{reinterpret_cast<const double*>(reinterpret_cast<uintptr_t>(h->st_emis.p) -
+                                                    (uintptr_t)base * (uintptr_t)N * 8),
+                    N};
+  st = decode_device(h, nseq, offsets, h->st_off.as<int64_t>(), nullptr, o, h->st_path.as<int32_t>(),
+                     h->st_score.as<double>(), h->st_status.as<uint8_t>(), stream, nullptr, false, nullptr, nullptr,
+                     nullptr, nullptr, &src);
+  if (st != CV_OK) {
+    (void)hipStreamSynchronize(stream);
+    return st;
+  }
+  if (total > base)
+    HIP_TRY(hipMemcpyAsync(path_out + base, h->st_path.as<int32_t>() + base, (size_t)(total - base) * 4,
+                           hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(score_out, h->st_score.p, (size_t)nseq * 8, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(status_out, h->st_status.p, (size_t)nseq, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
   return CV_OK;
 }
 

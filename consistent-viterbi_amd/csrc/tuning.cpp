@@ -18,7 +18,7 @@ struct Key {
 #define CVK_KEY(f) {#f, &Tuning::f}
 const Key kKeys[] = {
     CVK_KEY(trace), CVK_KEY(host_threads), CVK_KEY(t64_nonpos), CVK_KEY(generic_rows),
-    CVK_KEY(max_chunks), CVK_KEY(host_sums), CVK_KEY(no_trace), CVK_KEY(no_resume),
+    CVK_KEY(max_chunks), CVK_KEY(emis_overlap), CVK_KEY(host_sums), CVK_KEY(no_trace), CVK_KEY(no_resume),
     CVK_KEY(no_side), CVK_KEY(chain_par), CVK_KEY(chain_old), CVK_KEY(chain_par_force),
     CVK_KEY(chain_spec), CVK_KEY(chain_spec_kernel), CVK_KEY(chain_copy_overlap), CVK_KEY(chain_cert_fused),
     CVK_KEY(chain_parts), CVK_KEY(chain_tail), CVK_KEY(chain_tail_div), CVK_KEY(chain_spec_prio), CVK_KEY(chain_pin_obs), CVK_KEY(chain_pin_path), CVK_KEY(t64_s),

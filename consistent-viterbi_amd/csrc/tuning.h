@@ -21,6 +21,7 @@ struct Tuning {
   int t64_nonpos = 1;          // 0: the general f64 interval backtrack test (and no parallel chain)
   int generic_rows = 1;        // 0: the generic kernels in psi mode (inline argmax) instead of rows mode
   int max_chunks = 8;          // f32 trellis pipeline depth (1..64)
+  int emis_overlap = 0;        // 1: dense emissions on the f64 trellis: chunk k+1 staged beside chunk k's forward
   int host_sums = 0;           // 1: the constrained decode's exact unary sums on the host
   int no_trace = 0;            // 1: no certified suffix trace (the resume forward instead)
   int no_resume = 0;           // 1: no resume flow (the full forced decode)

@@ -44,6 +44,7 @@ EXPORTS = [
     "cv_hmm_set_tuning", "cv_hmm_get_tuning", "cv_tuning_key", "cv_hmm_release_workspaces",
     "cv_posterior_batch", "cv_posterior_batch_device",
     "cv_kbest_batch", "cv_kbest_batch_device",
+    "cv_decode_emissions", "cv_decode_emissions_device",
 ]
 
 
@@ -125,6 +126,8 @@ def lib():
         "cv_posterior_batch_device": ([P, I64, P, P, P, P, P, P, P, P], S),
         "cv_kbest_batch": ([P, I64, P, P, I32, P, P, P, P, P], S),
         "cv_kbest_batch_device": ([P, I64, P, P, P, I32, P, P, P, P, P], S),
+        "cv_decode_emissions": ([P, I64, P, P, I64, P, P, P, P], S),
+        "cv_decode_emissions_device": ([P, I64, P, P, P, I64, P, P, P, P], S),
         "cv_last_timing": ([P, P], S),
         "cv_timing_begin": ([P], S),
         "cv_timing_end": ([P, P], S),

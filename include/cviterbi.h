@@ -163,6 +163,10 @@ CV_API void cv_hmm_destroy(cv_hmm* h);
  *   t64_nonpos 1          0: the general f64 backtrack interval test (and no parallel chain)
  *   generic_rows 1        0: generic kernels in psi mode (inline argmax) instead of rows mode
  *   max_chunks 8          f32 trellis pipeline depth (1..64)
+ *   emis_overlap 0        1: cv_decode_emissions* on the f64 trellis, more than one chunk: the next chunk
+ *                         staged on a second stream beside the current forward pass, out of a second
+ *                         staging buffer under the same cap (2% faster at equal chunks; the cap then
+ *                         splits the batch into more chunks, which can cost far more: DESIGN.md)
  *   host_sums 0           1: the constrained decode's exact unary sums on the host
  *   no_trace / no_resume / no_side 0   1: no certified suffix trace / resume flow / side-stream decode
  *   chain_par 1           0: cv_decode_superseq_cp runs the serial chain kernel
@@ -474,6 +478,38 @@ CV_API cv_status cv_kbest_batch_device(cv_hmm* h, int64_t nseq, const int64_t* o
                                        const int64_t* offsets_dev, const int32_t* obs_dev, int32_t k,
                                        const cv_opts* opts, int32_t* path_dev, double* score_dev,
                                        int32_t* count_dev, uint8_t* status_dev);
+
+/* ---- decode of caller-supplied emission scores ------------------------------------------
+ * cv_decode_batch for observations that are not symbols of the handle's alphabet (continuous
+ * densities, scores of a tagger, back-off rows): the model (pi, A) is the handle's, its own b
+ * is ignored, and the emissions arrive per call as a dense array
+ *   emis[e * ld + j] = log10 p(observation of element e | state j),  j < N <= ld,
+ * e the element index of the CSR offsets (row e at emis + e * ld; ld is the row stride in
+ * doubles, rows need 8-byte alignment only).  Values may be positive (densities) or -inf.
+ * The result is, by definition, what cv_decode_batch with dtype CV_DTYPE_F64 gives for the
+ * discrete model b[j][e] = emis[e][j] with obs[e] = e: the same recurrence per association,
+ * first-index ties, statuses and scores, bit for bit (the same kernels decode staged rows).
+ * Per entry: -0.0 reads as +0.0; a sequence with a NaN or +inf in one of its rows gets
+ * CV_SEQ_BADOBS with the path and score cv_decode_batch_device reports for a sequence holding
+ * an out-of-range observation, and disturbs no other sequence.
+ * opts: dtype must be CV_DTYPE_F64 (CV_DTYPE_F32 is CV_EUNSUPPORTED); assoc any; kernel
+ * CV_KERNEL_AUTO / GENERIC / TRELLIS_F64 with cv_decode_batch's f64 selection rules
+ * (CV_KERNEL_TRELLIS is CV_EUNSUPPORTED); forced wherever cv_decode_batch supports it;
+ * workspace_bytes caps the delta rows plus the staged emissions of a chunk (8 P + 4 bytes per
+ * element more, P the kernel's table stride: NP for the f64 trellis, N otherwise).
+ * ld < N or a null pointer is CV_EINVAL.  cv_last_timing as for cv_decode_batch; fwd_ms and
+ * total_ms include the staging kernel.  Host pointers; synchronous. */
+CV_API cv_status cv_decode_emissions(cv_hmm* h, int64_t nseq, const int64_t* offsets, const double* emis,
+                                     int64_t ld, const cv_opts* opts, int32_t* path_out, double* score_out,
+                                     uint8_t* status_out);
+/* The same on device-resident buffers, with cv_decode_batch_device's contract: enqueued on
+ * opts->stream (or the handle's stream), returns after enqueueing; offsets_host (nullable) is a
+ * host copy of the offsets; opts->forced is a device pointer.  emis_dev is read in place (no
+ * copy besides the staging pass) and must stay valid until the call has run. */
+CV_API cv_status cv_decode_emissions_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
+                                            const int64_t* offsets_dev, const double* emis_dev, int64_t ld,
+                                            const cv_opts* opts, int32_t* path_dev, double* score_dev,
+                                            uint8_t* status_dev);
 
 /* ---- trait Solver (viterbi_solver.rs:11-16) -------------------------------------------
  * kind: "gpu"      f32 trellis kernel, VITERBI association, f64 re-scored objective
