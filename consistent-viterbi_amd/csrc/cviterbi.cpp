@@ -247,6 +247,15 @@ struct cv_hmm {
   int nonpos_cache = -1;    // model_nonpos(): the same predicate without the t64 tables (any N)
   double arc_max = -1.0;    // max finite |pi| or |a|, plus max finite |b| (< 0: not computed yet)
   double cert_rho_cap = 0.0;  // the parallel chain's certified backtrack (T64BtArgs::rho_cap)
+  // sparse low planes (tuning key t64_lo_every): the resolver's device counter block
+  // ([kT64StatSlots + 1][kT64StatWords] u64; the last slot holds the call's lo_every and
+  // sequence count) and its pinned host copy, made asynchronously after each plain batch decode
+  // on the f64 trellis, so it holds the last such call that has FINISHED.  t64_lo_off: the
+  // sticky guard -- a call that replayed densely more than once per 64 sequences (tie-heavy
+  // models) or failed a self-check pins the handle to full rows
+  DevBuf t64_stats;
+  PinnedHost t64_stats_pin;
+  bool t64_lo_off = false;
   DevBuf q_pi0;  // the reversed (suffix) pass: pi = 0 for the N states, -inf padding
   // f32 generic tables
   bool g32_ready = false;
@@ -762,6 +771,27 @@ cv_status stage_emissions(const cv_hmm* h, const EmisSrc& src, const int64_t* of
   return CV_OK;
 }
 
+// The resolver's counters as cv_last_t64_stats reports them, from the pinned copy: lo_every,
+// events, scans, rows descended, dense replays, self-check mismatches, largest need-set,
+// sequences (zeros before the first such call has finished).
+void t64_stats_sum(const cv_hmm* h, int64_t (&out)[8]) {
+  for (int64_t& v : out) v = 0;
+  const volatile uint64_t* p = static_cast<const volatile uint64_t*>(h->t64_stats_pin.p);
+  if (!p) return;
+  for (int sl = 0; sl < cvk::kT64StatSlots; ++sl) {
+    const volatile uint64_t* w = p + (size_t)sl * cvk::kT64StatWords;
+    out[1] += (int64_t)w[cvk::T64_STAT_EVENTS];
+    out[2] += (int64_t)w[cvk::T64_STAT_SCANS];
+    out[3] += (int64_t)w[cvk::T64_STAT_LEVELS];
+    out[4] += (int64_t)w[cvk::T64_STAT_OVERFLOWS];
+    out[5] += (int64_t)w[cvk::T64_STAT_MISMATCHES];
+    out[6] = std::max<int64_t>(out[6], (int64_t)w[cvk::T64_STAT_MAXNEED]);
+  }
+  const volatile uint64_t* meta = p + (size_t)cvk::kT64StatSlots * cvk::kT64StatWords;
+  out[0] = (int64_t)(meta[0] & 0xffffffffu);
+  out[7] = (int64_t)(meta[1] & 0xffffffffu);
+}
+
 // Core device-side decode.  All pointers are device pointers except offsets_host.
 // emis (cv_decode_emissions*, f64 only): the emissions of every element come from this dense
 // array instead of the handle's b through obs_dev (ignored, may be null): each chunk's rows are
@@ -773,7 +803,9 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
                         bool side_ws = false, double* cp_cert = nullptr, const double* cp_init = nullptr,
                         double* cp_last = nullptr,
                         std::vector<std::pair<int64_t, int64_t>>* chunks_out = nullptr,
-                        const EmisSrc* emis = nullptr) {
+                        const EmisSrc* emis = nullptr, bool batch_api = false) {
+  // batch_api (cv_decode_batch[_device] only): the f64 trellis may keep sparse low planes
+  // (tuning key t64_lo_every) and records the resolver's counters (cv_last_t64_stats)
   // cp_cert (the parallel CPSolver chain, row-A0 f64 trellis only): each chunk's backtrack
   // computes its certificates (or cp_cert_f64 reads the chunk's rows and paths) -> [nseq][2];
   // chunks_out: h->chunk_ev[i] is recorded after chunk i's backtrack (its paths written,
@@ -1054,6 +1086,33 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
     order_dev = w_order.as<int32_t>();
   }
 
+  // Sparse low planes (trellis64.h row contract): only where the forward and the backtrack are
+  // the plain NONPOS row-A0 pair and nothing else reads the rows -- no forced states, resume rows,
+  // chain certificates or chunk events, dense emissions, DPSolver / viterbi::decode rows -- at
+  // NP = 128 / 192 / 256.  Every other decode writes and reads full rows.
+  const bool t64_stats_on = batch_api && use_t64 && !t64cp && !side_ws;
+  int lo_every = 1;
+  if (t64_stats_on) {
+    constexpr size_t kStatBytes = (size_t)(cvk::kT64StatSlots + 1) * cvk::kT64StatWords * 8;
+    if (!h->t64_stats_pin.p) {
+      if (!h->t64_stats_pin.ensure(kStatBytes)) return set_err(CV_ENOMEM, "pinned f64 trellis counters failed");
+      std::memset(h->t64_stats_pin.p, 0, kStatBytes);
+    }
+    if ((st = h->t64_stats.ensure(kStatBytes)) != CV_OK) return st;
+    int64_t last[8];
+    t64_stats_sum(h, last);  // the previous call's counters if it has finished (no wait: else older ones)
+    if (last[0] > 1 && (last[4] * 64 > last[7] || last[5] > 0)) h->t64_lo_off = true;
+    const bool plain_pair = o.assoc == CV_ASSOC_VITERBI && !o.forced && !resume_rows && !cp_cert && !cp_init &&
+                            !cp_last && !chunks_out && !emis && h->t64_nonpos &&
+                            (h->np64 == 128 || h->np64 == 192 || h->np64 == 256);
+    if (plain_pair && !h->t64_lo_off)
+      lo_every = std::min(std::max(h->tuning.t64_lo_every, 1), cvk::kT64LoEveryMax);
+    HIP_TRY(hipMemsetAsync(h->t64_stats.p, 0, kStatBytes, stream));
+    uint32_t* meta = h->t64_stats.as<uint32_t>() + (size_t)cvk::kT64StatSlots * cvk::kT64StatWords * 2;
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(meta), lo_every, 1, stream));
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(meta + 2), (int)nseq, 1, stream));
+  }
+
   hipStream_t bts = serial ? stream : h->bt_stream;
   const size_t nev = 4 * chunks.size();
   // events of this call: from 0 (each call overwrites the last), or appended after the calls
@@ -1083,6 +1142,9 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
     ba.et = h->q_et.as<double>();
     ba.at32 = h->t64_nonpos ? h->q_at32.as<float>() : nullptr;
     if (emis) ba.at32 = nullptr;  // densities may be positive: the general f64 interval test
+    ba.lo_every = lo_every;
+    ba.a = h->q_a.as<double>();
+    ba.stats = h->t64_stats.as<unsigned long long>();
     return ba;
   };
   for (size_t ci = 0; ci < chunks.size(); ++ci) {
@@ -1157,6 +1219,7 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
       fa.dp_assoc = o.assoc == CV_ASSOC_DP ? 1 : 0;
       fa.forced = o.forced;
       fa.resume_rows = static_cast<const double*>(resume_rows);
+      fa.lo_every = lo_every;
       if (emis) fa.et = ev.et, fa.obs = ev.obs, fa.nobs = ev.nobs;
       const int spw = cvk::t64_seqs_per_wave(n, h->cus, h->np64);
       // the S actually launched: CP / DP, NP = 1,024 and forced NP = 512 run S <= 4 (launch_t64_fwd)
@@ -1391,6 +1454,9 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
   // the caller's stream sees the whole decode complete
   if (!serial) HIP_TRY(hipStreamWaitEvent(stream, evv[eb + 4 * (chunks.size() - 1) + 3], 0));
   if (!side_ws && h->acc_on) h->acc_used += nev;
+  if (t64_stats_on)  // the counters follow the last backtrack (t64 chunks run on `stream`); nobody waits for them
+    HIP_TRY(hipMemcpyAsync(h->t64_stats_pin.p, h->t64_stats.p, (size_t)(cvk::kT64StatSlots + 1) * cvk::kT64StatWords * 8,
+                           hipMemcpyDeviceToHost, stream));
   if (!ws_done) HIP_TRY(hipEventCreateWithFlags(&ws_done, hipEventDisableTiming));
   HIP_TRY(hipEventRecord(ws_done, stream));
   ws_rec = true;
@@ -1892,7 +1958,8 @@ CV_API cv_status cv_decode_batch_device(cv_hmm* h, int64_t nseq, const int64_t* 
   if (st != CV_OK) return st;
   const cv_opts o = opts ? *opts : default_opts();
   hipStream_t stream = o.stream ? (hipStream_t)o.stream : h->stream;
-  return decode_device(h, nseq, offsets_host, offsets_dev, obs_dev, o, path_dev, score_dev, status_dev, stream);
+  return decode_device(h, nseq, offsets_host, offsets_dev, obs_dev, o, path_dev, score_dev, status_dev, stream, nullptr,
+                       false, nullptr, nullptr, nullptr, nullptr, nullptr, true);
 }
 
 // Host-pointer decode; caller holds h->mu and has selected the device.
@@ -1900,7 +1967,7 @@ CV_API cv_status cv_decode_batch_device(cv_hmm* h, int64_t nseq, const int64_t* 
 // offsets[nseq]); forced_staged: o.forced is a validated DEVICE array indexed like obs.
 static cv_status decode_host_locked(cv_hmm* h, int64_t nseq, const int64_t* offsets, const int32_t* obs, cv_opts o,
                                     int32_t* path_out, double* score_out, uint8_t* status_out,
-                                    bool obs_staged = false, bool forced_staged = false) {
+                                    bool obs_staged = false, bool forced_staged = false, bool batch_api = false) {
   cv_status st;
   if (nseq == 0) return CV_OK;
   if ((st = check_batch(h, nseq, offsets)) != CV_OK) return st;
@@ -1934,7 +2001,8 @@ static cv_status decode_host_locked(cv_hmm* h, int64_t nseq, const int64_t* offs
     o.forced = h->st_forced.as<int32_t>();
   }
   st = decode_device(h, nseq, offsets, h->st_off.as<int64_t>(), h->st_obs.as<int32_t>(), o, h->st_path.as<int32_t>(),
-                     h->st_score.as<double>(), h->st_status.as<uint8_t>(), stream);
+                     h->st_score.as<double>(), h->st_status.as<uint8_t>(), stream, nullptr, false, nullptr, nullptr,
+                     nullptr, nullptr, nullptr, batch_api);
   if (st != CV_OK) {
     (void)hipStreamSynchronize(stream);
     return st;
@@ -1956,7 +2024,8 @@ CV_API cv_status cv_decode_batch(cv_hmm* h, int64_t nseq, const int64_t* offsets
   CV_LOCK(h);
   cv_status st = set_device(h);
   if (st != CV_OK) return st;
-  return decode_host_locked(h, nseq, offsets, obs, opts ? *opts : default_opts(), path_out, score_out, status_out);
+  return decode_host_locked(h, nseq, offsets, obs, opts ? *opts : default_opts(), path_out, score_out, status_out,
+                            false, false, true);
 }
 
 CV_API cv_status cv_posterior_batch_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
@@ -3581,6 +3650,17 @@ CV_API cv_status cv_last_superseq_stats(const cv_hmm* h, int64_t* out) {
   if (!h || !out) return set_err(CV_EINVAL, "null argument");
   for (int q = 0; q < 9; ++q) out[q] = h->last_chain[q];
   return CV_OK;
+}
+
+CV_API int32_t cv_last_t64_stats(const cv_hmm* h, int64_t* out, int32_t n) {
+  if (!h || n < 0 || (n > 0 && !out)) {
+    set_err(CV_EINVAL, "bad argument");
+    return -1;
+  }
+  int64_t v[8];
+  t64_stats_sum(h, v);
+  for (int32_t q = 0; q < n && q < 8; ++q) out[q] = v[q];
+  return 8;
 }
 
 CV_API cv_status cv_last_suffix_traced(const cv_hmm* h, int64_t* out) {

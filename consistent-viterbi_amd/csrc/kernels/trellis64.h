@@ -51,7 +51,22 @@ struct T64FwdArgs {
   // steps in a per-SIMD table and takes issue priority 3 if no other wave of its SIMD has more
   // work left, else 1 (the arbiter runs the oldest wave first among equals); 0 = off
   int balance;
+  // sparse low planes (see the row contract below): 0 / 1 = every row carries both planes;
+  // K > 1 = the low plane only at rows t % K == 0 and at each sequence's last row.  Only the
+  // batch decode's kernels read it (trellis_fwd_f64 without EXT and the DPSolver association,
+  // trellis_fwd_f64_rs); every other forward kernel writes full rows whatever it holds
+  int lo_every;
 };
+
+// the sparse resolver's limits (backtrack_f64 SPARSE): lo_every <= kT64LoEveryMax rows between
+// full rows, need-sets of at most kT64NeedCap states per row
+constexpr int kT64LoEveryMax = 16;
+constexpr int kT64NeedCap = 8;
+// device counter block of the resolver: kT64StatSlots slots (one 64-byte line each, chosen by
+// workgroup, so the atomics spread over the L2 channels) of kT64StatWords words
+constexpr int kT64StatSlots = 32;
+constexpr int kT64StatWords = 8;
+enum { T64_STAT_EVENTS = 0, T64_STAT_SCANS, T64_STAT_LEVELS, T64_STAT_OVERFLOWS, T64_STAT_MISMATCHES, T64_STAT_MAXNEED };
 
 struct T64BtArgs {
   const double* delta;
@@ -76,6 +91,14 @@ struct T64BtArgs {
   double* cert;            // non-null (NONPOS row A0, NP <= 256): the parallel chain's certificate
                            // (rho, gF) per sequence [2 nseq], as cp_cert_f64 computes it
   double rho_cap;          // steps whose estimated certificate term reaches it skip the exact gap
+  // sparse low planes (K = lo_every > 1; the plain NONPOS row-A0 kernel only: at32 set, no
+  // dp_assoc / decode_bt / cert, NP in {128, 192, 256} -- launch_t64_bt refuses anything else):
+  // the rows were written by a forward pass with the same lo_every, and a near tie at a row
+  // without a low plane goes through the sparse resolver (bt_chain_f64 SPARSE), which needs obs
+  // and et above, the from-major table and a counter block
+  int lo_every;
+  const double* a;            // [NP][NP] a[i][j] (the resolver's dense replay)
+  unsigned long long* stats;  // [kT64StatSlots][kT64StatWords] counters (T64_STAT_*), atomically added to
 };
 
 // Delta rows of the f64 trellis (forward -> backtrack, resume-flow prefix rows) use a
@@ -83,6 +106,18 @@ struct T64BtArgs {
 // [NP, 2 NP) their low words (8*NP bytes per row, like a plain f64 row).  The backtrack reads
 // the high plane only (a 20-bit-mantissa truncation with a rigorous error bound) and the low
 // plane only on near ties.
+//
+// ROW CONTRACT.  The high plane of every row is always written.  A row is FULL when its low
+// plane is written too.  With lo_every <= 1 every row is full.  With lo_every = K > 1 (the batch
+// decode's plain NONPOS row-A0 pair only) row t of a sequence of T rows is full iff t % K == 0
+// or t == T - 1: row 0 and the last row always are, so the score and the last row's first argmax
+// never need the resolver, and the nearest full row at or before row r is r - r % K, at most
+// K - 1 rows away.  The low words of the other rows are NEVER READ (they hold whatever the
+// workspace held); the row stride stays 2*NP words.  Every other producer of these rows -- the
+// EXT passes, the DPSolver association, viterbi::decode's zero_init rows, the one-wave N <= 64
+// kernels, NP >= 512 -- writes full rows, and every other consumer (cp_cert_f64, the certified
+// backtrack, suffix_trace_f64, the resume flow, prefix_backtrack_f64) is only ever given full
+// rows.
 
 struct PrefixBt64Args {
   const double* rows;       // compact split-plane prefix rows (the terms pass's prefix launch)

@@ -70,30 +70,42 @@ __device__ __forceinline__ sptr<T> scalar_view(const T* p) {
 }
 
 
-// C f64 as two planes of C words each (dwordx4 / dwordx2 stores), non-temporal
+// C f64 as two planes of C words each (dwordx4 / dwordx2 stores), non-temporal; with_lo
+// (wave-uniform) = false leaves the low plane unwritten (sparse rows: T64FwdArgs::lo_every)
 template <int C>
-__device__ __forceinline__ void store_split(uint32_t* hi, uint32_t* lo, const double (&v)[C]) {
+__device__ __forceinline__ void store_split(uint32_t* hi, uint32_t* lo, const double (&v)[C], bool with_lo = true) {
   if constexpr (C % 4 == 0) {
 #pragma unroll
     for (int c = 0; c < C; c += 4) {
       u32x4 h = {hi_word(v[c]), hi_word(v[c + 1]), hi_word(v[c + 2]), hi_word(v[c + 3])};
-      u32x4 l = {lo_word(v[c]), lo_word(v[c + 1]), lo_word(v[c + 2]), lo_word(v[c + 3])};
       __builtin_nontemporal_store(h, reinterpret_cast<u32x4*>(hi + c));
-      __builtin_nontemporal_store(l, reinterpret_cast<u32x4*>(lo + c));
+    }
+    if (with_lo) {
+#pragma unroll
+      for (int c = 0; c < C; c += 4) {
+        u32x4 l = {lo_word(v[c]), lo_word(v[c + 1]), lo_word(v[c + 2]), lo_word(v[c + 3])};
+        __builtin_nontemporal_store(l, reinterpret_cast<u32x4*>(lo + c));
+      }
     }
   } else if constexpr (C % 2 == 0) {
 #pragma unroll
     for (int c = 0; c < C; c += 2) {
       u32x2 h = {hi_word(v[c]), hi_word(v[c + 1])};
-      u32x2 l = {lo_word(v[c]), lo_word(v[c + 1])};
       __builtin_nontemporal_store(h, reinterpret_cast<u32x2*>(hi + c));
-      __builtin_nontemporal_store(l, reinterpret_cast<u32x2*>(lo + c));
+    }
+    if (with_lo) {
+#pragma unroll
+      for (int c = 0; c < C; c += 2) {
+        u32x2 l = {lo_word(v[c]), lo_word(v[c + 1])};
+        __builtin_nontemporal_store(l, reinterpret_cast<u32x2*>(lo + c));
+      }
     }
   } else {
 #pragma unroll
-    for (int c = 0; c < C; ++c) {
-      __builtin_nontemporal_store(hi_word(v[c]), hi + c);
-      __builtin_nontemporal_store(lo_word(v[c]), lo + c);
+    for (int c = 0; c < C; ++c) __builtin_nontemporal_store(hi_word(v[c]), hi + c);
+    if (with_lo) {
+#pragma unroll
+      for (int c = 0; c < C; ++c) __builtin_nontemporal_store(lo_word(v[c]), lo + c);
     }
   }
 }
@@ -357,6 +369,12 @@ __global__ __launch_bounds__(64 * W * WG) __attribute__((amdgpu_waves_per_eu(MIN
     const double* row = g.et + (size_t)o * NP + j0;
     load_a<C>(row, e);
   };
+  // sparse rows (T64FwdArgs::lo_every = K > 1, batch decode only): the low plane is written at
+  // rows t % K == 0 and at each sequence's last row; lo_step = this step's t % K == 0, kept by a
+  // scalar counter (lo_phase) so the step costs no division
+  const int lo_k = (!EXT && !DPA && !DEFST && g.lo_every > 1) ? g.lo_every : 1;
+  int lo_phase = 0;
+  bool lo_step = true;
   auto store_row = [&](int s, int t, const double (&v)[C]) {
     const int64_t r = (int64_t)((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)my_rb, s) |
                                 ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(my_rb >> 32), s) << 32));
@@ -373,7 +391,7 @@ __global__ __launch_bounds__(64 * W * WG) __attribute__((amdgpu_waves_per_eu(MIN
 #else  // ablation build (timing only): every step of a sequence overwrites its first row (L2-resident)
       uint32_t* dst = reinterpret_cast<uint32_t*>(g.delta) + r * (2 * NP) + j0;
 #endif
-      store_split<C>(dst, dst + NP, v);
+      store_split<C>(dst, dst + NP, v, lo_step || t == T[s] - 1);
     }
     if (EXT && g.last_row && t == T[s] - 1) {
       const int64_t k = (int64_t)__builtin_amdgcn_readlane((int)(uint32_t)(my_slot - g.seq_begin), s);
@@ -459,6 +477,8 @@ __global__ __launch_bounds__(64 * W * WG) __attribute__((amdgpu_waves_per_eu(MIN
   SimdBalance sb;
   sb.init(bal > 0, lane, Tmax - 1);
   for (int t = 1; t < Tmax; ++t) {
+    lo_phase = lo_phase + 1 == lo_k ? 0 : lo_phase + 1;
+    lo_step = lo_phase == 0;
     const unsigned ocur_l = obs_use(onext_l, t);
     const int fcur_l = frc_use(fnext_l);
     double ecur[DPA ? S : 1][C];
@@ -747,12 +767,16 @@ __global__ __launch_bounds__(512) void trellis_fwd_f64_rs(T64FwdArgs g) {
   auto emis = [&](unsigned o, double (&e)[C]) { load_a<C>(g.et + (size_t)o * NP + j0, e); };
   // own sequence sown + q (q < HS): length, delta row base (uniform, from its lane)
   auto seq_T = [&](int q) { return __builtin_amdgcn_readlane(my_T, sown + q); };
+  // sparse rows (T64FwdArgs::lo_every), as trellis_fwd_f64
+  const int lo_k = g.lo_every > 1 ? g.lo_every : 1;
+  int lo_phase = 0;
+  bool lo_step = true;
   auto store_row = [&](int q, int t, const double (&v)[C]) {
     if (g.delta && t < seq_T(q)) {
       const int64_t r = (int64_t)((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)my_rb, sown + q) |
                                   ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(my_rb >> 32), sown + q) << 32));
       uint32_t* dst = reinterpret_cast<uint32_t*>(g.delta) + (r + t) * (2 * NP) + j0;
-      store_split<C>(dst, dst + NP, v);
+      store_split<C>(dst, dst + NP, v, lo_step || t == seq_T(q) - 1);
     }
   };
   // acc of own (partner = false) or partner sequence q of this wave (selects: no runtime
@@ -788,6 +812,8 @@ __global__ __launch_bounds__(512) void trellis_fwd_f64_rs(T64FwdArgs g) {
     __builtin_amdgcn_sched_barrier(0);
   }
   for (int t = 1; t < Tmax; ++t) {
+    lo_phase = lo_phase + 1 == lo_k ? 0 : lo_phase + 1;
+    lo_step = lo_phase == 0;
     const unsigned ocur_l = obs_use(onext_l, t);
 #pragma unroll
     for (int c = 0; c < C; ++c)
@@ -1163,16 +1189,263 @@ __device__ __forceinline__ int first_argmax_d(const double (&s)[KP], const bool 
 // cp_cert_f64 does.  So the returned rho equals cp_cert_f64's exact rho whenever that is below
 // rho_cap, and is >= rho_cap otherwise: the host's tests rho > U agree with the exact
 // certificate for every U <= rho_cap (the host sizes rho_cap above the largest U it can test).
+//
+// SPARSE (plain NONPOS row A0 only; rows written with T64FwdArgs::lo_every = K > 1, see the row
+// contract in trellis64.h): row t-1 has a low plane only if (t-1) % K == 0.  At a near tie on
+// another row the survivors of the threshold test are the only candidates that can attain the
+// exact maximum (the test's own bound: s_i >= max s implies x_i >= thr), so only THEIR exact
+// delta_{t-1}[i] are needed, and the sparse resolver recomputes them from the nearest full row
+// c = (t-1) - (t-1) % K:
+//   descend: for each needed (row r, state i) the same threshold scan runs over the high plane
+//     of row r-1 against at32[i][.]; the survivors (the only k that can attain delta_r[i]'s
+//     maximum) join the need-set of row r-1 -- a union over i, kept as ballot masks, at most
+//     kT64NeedCap states -- down to row c;
+//   ascend: exact(c, k) from both planes; exact(r, i) = max over the need-set of row r-1 of
+//     (exact(r-1, k) + a[k][i]), then + et[obs[r]][i]: the forward pass's association and f64
+//     adds, and a maximum is order-free, so the value is the forward's bit for bit (the union may
+//     hold more than i's own survivors: true candidates too, never above the maximum).  Self-check:
+//     the high word of every resolved value equals the stored one;
+//   choose: the first index among the step's survivors with the largest exact sum.
+// A need-set above the cap (exact ties: dyadic models), a failed self-check or an all -inf
+// maximum take the DENSE REPLAY: this wave runs the forward recurrence over rows c+1 .. t-1 for
+// its one sequence (delta in LDS, A rows from L2) -- exact by construction, no host round trip.
+// Counters (events, scans, rows descended, replays, mismatches, largest need-set) go to
+// T64BtArgs::stats.
+
+// The exact step of the SPARSE chain (see bt_chain_f64 SPARSE): the predecessor of `cur` at step
+// t when the threshold test found a near tie.  OUT OF LINE on purpose, and self-contained: it
+// takes only (kernarg pointer, rows, lane, t, cur), reads everything else from the kernel's own
+// argument block (backtrack_f64's one parameter is the T64BtArgs at offset 0), owns its
+// LDS and adds its counters to T64BtArgs::stats itself, so the chain's hot loop carries no state
+// for it -- inlined, or called with the pointers and estimates as arguments, it cost the chain
+// its eight waves per SIMD (112 VGPRs, or 60 spills at 64) and the backtrack 6.1 -> 9.2 ms at
+// config 4.  It runs at ~0.5% of the steps.  All control flow is wave-uniform.
+//   row t-1 full ((t-1) % K == 0): both planes are read and the exact f64 sums decide;
+//   otherwise the sparse resolver (descend / ascend / dense replay) recomputes what is missing.
+template <int KP>
+__device__ __attribute__((noinline)) int sparse_exact_step(const uint64_t kernarg_in, const uint32_t* rows_in,
+                                                           const int lane, const int t_in, const int cur_in) {
+  constexpr int NP = 64 * KP, CAP = kT64NeedCap;
+  constexpr uint32_t NINF_HI = 0xFFF00000u;
+  // per wave of the 256-thread workgroup: need-sets [level][CAP] (-1 = unused), the exact values
+  // of two consecutive levels, the dense replay's two rows
+  __shared__ int s_need[4][kT64LoEveryMax * CAP];
+  __shared__ double s_ex[4][2 * CAP];
+  __shared__ double s_row[4][2 * NP];
+  // arguments arrive in VGPRs: the wave-uniform ones back into scalars
+  auto uniform64 = [](uint64_t v) {
+    return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v) |
+           ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32);
+  };
+  // the kernel's argument block: the caller's kernarg segment pointer (the builtin itself is only
+  // valid in the kernel function -- in a callee it folds to null)
+  const sptr<T64BtArgs> g = (sptr<T64BtArgs>)uniform64(kernarg_in);
+  const int t = __builtin_amdgcn_readfirstlane(t_in), cur0 = __builtin_amdgcn_readfirstlane(cur_in);
+  const uint32_t* __restrict__ rows = reinterpret_cast<const uint32_t*>((uintptr_t)uniform64((uint64_t)(uintptr_t)rows_in));
+  const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  const int K = g->lo_every, N = g->nstates;
+  const double* __restrict__ at = g->at;
+  const float* __restrict__ at32 = g->at32;
+  const double* __restrict__ et = g->et;
+  // the sequence's first element, from its first row: rows = delta + (e0 - delta_elem_base) rows
+  const int64_t e0 = (rows - reinterpret_cast<const uint32_t*>(g->delta)) / (2 * NP) + g->delta_elem_base;
+  const int32_t* __restrict__ obs = g->obs + e0;
+  volatile int* need = s_need[w];
+  volatile double* ex = s_ex[w];
+  volatile double* rw = s_row[w];
+  bool valid[KP];
+#pragma unroll
+  for (int k = 0; k < KP; ++k) valid[k] = (lane + 64 * k) < N;
+  const int r0 = t - 1;
+  // the step's own threshold test again (the same operations on the same words: the same survivors)
+  uint32_t hw0[KP];
+  unsigned long long m0[KP];
+  int cnt0 = 0;
+  {
+    float x[KP];
+    float lm = -__builtin_inff();
+#pragma unroll
+    for (int k = 0; k < KP; ++k) {
+      hw0[k] = valid[k] ? rows[(size_t)r0 * (2 * NP) + lane + 64 * k] : NINF_HI;
+      x[k] = (float)from_words(hw0[k], 0u) + at32[(size_t)cur0 * NP + lane + 64 * k];
+      lm = __builtin_fmaxf(lm, x[k]);
+    }
+    const float M = wave_max_f32(lm);
+    const float thr = M * (1.0f + 0x3p-20f) - 0x1p-100f;
+#pragma unroll
+    for (int k = 0; k < KP; ++k) {
+      m0[k] = __ballot(x[k] >= thr);
+      cnt0 += __builtin_popcountll(m0[k]);
+    }
+  }
+  if (K <= 1 || r0 % K == 0) {  // a full row: the exact f64 sums of this row decide (first index)
+    const double* acol = at + (size_t)cur0 * NP + lane;
+    double sx[KP];
+#pragma unroll
+    for (int k = 0; k < KP; ++k)
+      sx[k] = valid[k] ? from_words(hw0[k], rows[(size_t)r0 * (2 * NP) + NP + lane + 64 * k]) + acol[64 * k] : ninf_d();
+    double Md;
+    return first_argmax_d<KP>(sx, valid, Md);
+  }
+  const int c = r0 - r0 % K, D = r0 - c;  // the nearest full row, 1 <= D < K rows down
+  const unsigned long long below = (1ull << lane) - 1;
+  unsigned scans = 0, levels = 0, maxneed = (unsigned)cnt0;
+  auto count = [&](bool replay, bool mismatch) {
+    if (lane == 0) {
+      unsigned long long* st = g->stats + (size_t)(blockIdx.x % kT64StatSlots) * kT64StatWords;
+      atomicAdd(st + T64_STAT_EVENTS, 1ull);
+      if (scans) atomicAdd(st + T64_STAT_SCANS, (unsigned long long)scans);
+      if (levels) atomicAdd(st + T64_STAT_LEVELS, (unsigned long long)levels);
+      if (replay) atomicAdd(st + T64_STAT_OVERFLOWS, 1ull);
+      if (mismatch) atomicAdd(st + T64_STAT_MISMATCHES, 1ull);
+      atomicMax(st + T64_STAT_MAXNEED, (unsigned long long)maxneed);
+    }
+  };
+  bool ok = cnt0 <= CAP, mismatch = false;
+  int n = cnt0;
+  if (ok) {
+    // the need-set of row r0: the step's survivors in ascending order
+    if (lane < CAP) need[lane] = -1;
+    int base = 0;
+#pragma unroll
+    for (int k = 0; k < KP; ++k) {
+      if ((m0[k] >> lane) & 1) need[base + __builtin_popcountll(m0[k] & below)] = 64 * k + lane;
+      base += __builtin_popcountll(m0[k]);
+    }
+    __builtin_amdgcn_wave_barrier();
+#pragma nounroll
+    for (int d = 0; d < D; ++d) {  // descend: need[d] (row r0 - d) -> need[d + 1] (row r0 - d - 1)
+      float hf[KP];  // the high plane of row r0 - d - 1 (padded candidates: -inf)
+#pragma unroll
+      for (int k = 0; k < KP; ++k)
+        hf[k] = (float)from_words(valid[k] ? rows[(size_t)(r0 - d - 1) * (2 * NP) + lane + 64 * k] : NINF_HI, 0u);
+      unsigned long long m[KP];
+#pragma unroll
+      for (int k = 0; k < KP; ++k) m[k] = 0;
+#pragma nounroll
+      for (int q = 0; q < n; ++q) {
+        const int i = __builtin_amdgcn_readfirstlane(need[d * CAP + q]);
+        const float* acol32 = at32 + (size_t)i * NP + lane;
+        float xs[KP];
+        float lm = -__builtin_inff();
+#pragma unroll
+        for (int k = 0; k < KP; ++k) {
+          xs[k] = hf[k] + acol32[64 * k];
+          lm = __builtin_fmaxf(lm, xs[k]);
+        }
+        const float M = wave_max_f32(lm);
+        const float thr = M * (1.0f + 0x3p-20f) - 0x1p-100f;
+#pragma unroll
+        for (int k = 0; k < KP; ++k) m[k] |= __ballot(xs[k] >= thr);
+        ++scans;
+      }
+      ++levels;
+      int n2 = 0;
+#pragma unroll
+      for (int k = 0; k < KP; ++k) n2 += __builtin_popcountll(m[k]);
+      maxneed = (unsigned)n2 > maxneed ? (unsigned)n2 : maxneed;
+      if (n2 > CAP) {
+        ok = false;
+        break;
+      }
+      if (lane < CAP) need[(d + 1) * CAP + lane] = -1;
+      base = 0;
+#pragma unroll
+      for (int k = 0; k < KP; ++k) {
+        if ((m[k] >> lane) & 1) need[(d + 1) * CAP + base + __builtin_popcountll(m[k] & below)] = 64 * k + lane;
+        base += __builtin_popcountll(m[k]);
+      }
+      __builtin_amdgcn_wave_barrier();
+      n = n2;
+    }
+  }
+  if (ok) {
+    // the full row c: exact values of need[D] from both planes (lane q = entry q)
+    if (lane < CAP) {
+      const int k = need[D * CAP + lane];
+      const size_t q = (size_t)c * (2 * NP) + (k >= 0 ? k : 0);
+      ex[(D & 1) * CAP + lane] = k >= 0 ? from_words(rows[q], rows[q + NP]) : ninf_d();
+    }
+    __builtin_amdgcn_wave_barrier();
+    // ascend: lane 8 ii + kk adds entry kk of row r - 1 to a[k][i] of entry ii of row r
+    const int ii = lane >> 3, kk = lane & 7;
+    bool bad = false;
+#pragma nounroll
+    for (int d = D - 1; d >= 0; --d) {
+      const int r = r0 - d;
+      const int i = need[d * CAP + ii], k = need[(d + 1) * CAP + kk];
+      double v = (i >= 0 && k >= 0) ? ex[((d + 1) & 1) * CAP + kk] + at[(size_t)i * NP + k] : ninf_d();
+      v = fmax(v, __shfl_xor(v, 1));
+      v = fmax(v, __shfl_xor(v, 2));
+      v = fmax(v, __shfl_xor(v, 4));
+      if (i >= 0) {
+        v += et[(size_t)obs[r] * NP + i];  // (d + a) + b: viterbi.rs:15-17
+        bad = bad || hi_word(v) != rows[(size_t)r * (2 * NP) + i];
+      }
+      if (kk == 0) ex[(d & 1) * CAP + ii] = i >= 0 ? v : ninf_d();
+      __builtin_amdgcn_wave_barrier();
+    }
+    if (__ballot(bad)) {
+      mismatch = true;
+    } else {
+      const int i = lane < CAP ? need[lane] : -1;
+      const double sx = i >= 0 ? ex[lane < CAP ? lane : 0] + at[(size_t)cur0 * NP + i] : ninf_d();
+      const double M = wave_max_d(sx);
+      const unsigned long long mm = __ballot(i >= 0 && sx == M);
+      // need[0] ascends, so the lowest lane holding the maximum is the first index
+      if (M > ninf_d() && mm) {
+        count(false, false);
+        return __shfl(i, __builtin_ctzll(mm));
+      }
+    }
+  }
+  // dense replay of rows c + 1 .. r0 from the full row c
+  count(true, mismatch);
+#pragma unroll
+  for (int k = 0; k < KP; ++k) {
+    const size_t q = (size_t)c * (2 * NP) + lane + 64 * k;
+    rw[lane + 64 * k] = from_words(rows[q], rows[q + NP]);
+  }
+  __builtin_amdgcn_wave_barrier();
+  const double* __restrict__ ap = g->a + lane;
+#pragma nounroll
+  for (int r = c + 1; r <= r0; ++r) {
+    volatile double* src = rw + ((r - c - 1) & 1) * NP;
+    volatile double* dst = rw + ((r - c) & 1) * NP;
+    double m[KP];
+#pragma unroll
+    for (int k = 0; k < KP; ++k) m[k] = ninf_d();
+#pragma nounroll
+    for (int i = 0; i < NP; ++i) {
+      const double di = src[i];
+#pragma unroll
+      for (int k = 0; k < KP; ++k) m[k] = fmax(m[k], di + ap[(size_t)i * NP + 64 * k]);  // viterbi.rs:15-16
+    }
+    const double* e = et + (size_t)obs[r] * NP + lane;
+#pragma unroll
+    for (int k = 0; k < KP; ++k) dst[lane + 64 * k] = m[k] + e[64 * k];
+    __builtin_amdgcn_wave_barrier();
+  }
+  volatile double* fin = rw + ((r0 - c) & 1) * NP;
+  const double* acol = at + (size_t)cur0 * NP + lane;
+  double sx[KP];
+#pragma unroll
+  for (int k = 0; k < KP; ++k) sx[k] = valid[k] ? fin[lane + 64 * k] + acol[64 * k] : ninf_d();
+  double Md;
+  return first_argmax_d<KP>(sx, valid, Md);
+}
+
 #ifndef CVK_BT_ROLL
 #define CVK_BT_ROLL 0
 #endif
-template <int KP, int PF, bool DEC = false, bool NONPOS = false, bool CERT = false>
+template <int KP, int PF, bool DEC = false, bool NONPOS = false, bool CERT = false, bool SPARSE = false>
 __device__ __forceinline__ void bt_chain_f64(const uint32_t* __restrict__ rows, int T, int cur, int32_t* __restrict__ path,
                                              const double* __restrict__ at, const double* __restrict__ et,
                                              const int32_t* __restrict__ obs, int dp_assoc, int N, int lane,
                                              const float* __restrict__ at32 = nullptr, double* rho_io = nullptr,
                                              double u0 = 0.0, double rho_cap = 0.0) {
   static_assert(!CERT || (NONPOS && !DEC), "certificates: the NONPOS row-A0 chain");
+  static_assert(!SPARSE || (NONPOS && !DEC && !CERT), "sparse low planes: the plain NONPOS row-A0 chain");
   double rho = CERT ? *rho_io : 0.0;
   constexpr int NP = 64 * KP;
   constexpr uint32_t NINF_HI = 0xFFF00000u;  // hi word of -inf (lo word 0)
@@ -1261,6 +1534,10 @@ __device__ __forceinline__ void bt_chain_f64(const uint32_t* __restrict__ rows, 
         }
         if (!exact) {
           cur = idx;
+        } else if (SPARSE) {  // the exact step out of line (full row or sparse resolver)
+          // (bt_chain_f64 is inlined into backtrack_f64: the builtin is the kernel's own pointer)
+          if constexpr (SPARSE)
+            cur = sparse_exact_step<KP>((uint64_t)__builtin_amdgcn_kernarg_segment_ptr(), rows, lane, t, cur);
         } else {  // near tie (or a certificate step below rho_cap): the exact f64 sums decide (first index)
           const double* acol = at + (size_t)cur * NP + lane;
           uint32_t lw[KP];
@@ -1352,7 +1629,7 @@ __device__ __forceinline__ void bt_chain_f64(const uint32_t* __restrict__ rows, 
 // fused N <= 64 kernel: a uniform load of g.status could come from a stale scalar-cache line)
 // CERT: the chain certificate (rho, gF) of cp_cert_f64 into g.cert[2 seq], computed along the way
 // (bt_chain_f64 CERT); -1 for sequences that are not OK.
-template <int KP, int PF, bool NONPOS, bool CERT = false>
+template <int KP, int PF, bool NONPOS, bool CERT = false, bool SPARSE = false>
 __device__ __forceinline__ void backtrack_one_f64(const T64BtArgs& g, int64_t slot, int lane, int prior_in = -1) {
   constexpr int NP = 64 * KP;
   const int64_t seq = g.order ? (int64_t)g.order[slot] : slot;
@@ -1414,6 +1691,8 @@ __device__ __forceinline__ void backtrack_one_f64(const T64BtArgs& g, int64_t sl
   if constexpr (CERT)
     bt_chain_f64<KP, PF, false, true, true>(rows, T, cur, path, g.at, g.et, g.obs + e0, g.dp_assoc, N, lane, g.at32,
                                             &rho, u0, g.rho_cap);
+  else if constexpr (SPARSE)
+    bt_chain_f64<KP, PF, false, true, false, true>(rows, T, cur, path, g.at, g.et, g.obs + e0, 0, N, lane, g.at32);
   else if constexpr (NONPOS)
     bt_chain_f64<KP, PF, false, true>(rows, T, cur, path, g.at, g.et, g.obs + e0, g.dp_assoc, N, lane, g.at32);
   else
@@ -1436,9 +1715,16 @@ __device__ __forceinline__ void backtrack_one_f64(const T64BtArgs& g, int64_t sl
 // NONPOS at NP = 64: the f32 a^T (16 KiB) is staged in LDS, so the one dependent read of each
 // chain step is an LDS round trip instead of an L2 one (the longest chains set the makespan
 // of ragged batches, config 3).
-template <int KP, int PF, bool NONPOS = false, bool CERT = false>
-__global__ __launch_bounds__(256) void backtrack_f64(T64BtArgs g) {
-  constexpr bool LDS_AT = NONPOS && KP == 1;
+// SPARSE: the rows carry low planes at every lo_every-th row only (bt_chain_f64 SPARSE); the
+// out-of-line exact step (sparse_exact_step) brings its own LDS (per wave: need-sets, two levels
+// of exact values, two replay rows: 4.6 KiB at NP = 256) and reads this kernel's argument block
+// through the kernarg segment pointer: T64BtArgs must stay the kernel's only parameter.
+// (The call must not cost the chain its occupancy: where the plain kernel runs eight waves per
+// SIMD -- 60 VGPRs at KP = 4, PF = 2 -- the SPARSE one is held to eight too.)
+template <int KP, int PF, bool NONPOS = false, bool CERT = false, bool SPARSE = false>
+__global__ __launch_bounds__(256)
+__attribute__((amdgpu_waves_per_eu((SPARSE && (PF == 2 || (KP <= 2 && PF <= 8))) ? 8 : 1))) void backtrack_f64(T64BtArgs g) {
+  constexpr bool LDS_AT = NONPOS && KP == 1 && !SPARSE;
   __shared__ float at_lds[LDS_AT ? 64 * 64 : 1];
   if constexpr (LDS_AT) {
     for (int k = threadIdx.x; k < 64 * 64; k += 256) at_lds[k] = g.at32[k];
@@ -1447,7 +1733,11 @@ __global__ __launch_bounds__(256) void backtrack_f64(T64BtArgs g) {
   }
   const int lane = threadIdx.x & 63;
   const int64_t slot0 = g.seq_begin + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (slot0 < g.seq_end) backtrack_one_f64<KP, PF, NONPOS, CERT>(g, slot0, lane);
+  if constexpr (SPARSE) {
+    if (slot0 < g.seq_end) backtrack_one_f64<KP, PF, true, false, true>(g, slot0, lane);
+  } else {
+    if (slot0 < g.seq_end) backtrack_one_f64<KP, PF, NONPOS, CERT>(g, slot0, lane);
+  }
 }
 
 // Resume flow (f64): the prefix [offsets[seq], t1] of every constrained sequence backtracked
@@ -2253,6 +2543,21 @@ hipError_t bt_pf(int np, const T64BtArgs& ba, dim3 grid, dim3 block, hipStream_t
       default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
+  }
+  if (ba.lo_every > 1) {  // sparse low planes: the plain NONPOS row-A0 kernel with the resolver
+    if (!ba.at32 || ba.dp_assoc || ba.decode_bt || ba.lo_every > kT64LoEveryMax || !ba.a || !ba.stats || !ba.obs ||
+        !ba.et)
+      return hipErrorInvalidValue;
+    if constexpr (PF <= 16) {
+      switch (np) {
+        case 128: hipLaunchKernelGGL((backtrack_f64<2, PF, true, false, true>), grid, block, 0, stream, ba); break;
+        case 192: hipLaunchKernelGGL((backtrack_f64<3, PF, true, false, true>), grid, block, 0, stream, ba); break;
+        case 256: hipLaunchKernelGGL((backtrack_f64<4, PF, true, false, true>), grid, block, 0, stream, ba); break;
+        default: return hipErrorInvalidValue;
+      }
+      return hipGetLastError();
+    }
+    return hipErrorInvalidValue;
   }
   if (ba.at32) {
     hipError_t e = bt_pf_np<PF, true>(np, ba, grid, block, stream);

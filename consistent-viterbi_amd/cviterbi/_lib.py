@@ -45,6 +45,7 @@ EXPORTS = [
     "cv_posterior_batch", "cv_posterior_batch_device",
     "cv_kbest_batch", "cv_kbest_batch_device",
     "cv_decode_emissions", "cv_decode_emissions_device",
+    "cv_last_t64_stats",
 ]
 
 
@@ -142,6 +143,7 @@ def lib():
         "cv_viterbi_decode": ([P, I64, P, P], S),
         "cv_decode_superseq_cp": ([P, I64, P, P, P, P], S),
         "cv_last_superseq_stats": ([P, P], S),
+        "cv_last_t64_stats": ([P, P, I32], I32),
         "cv_device_memory": ([P, P], S),
         "cv_solver_create": ([ctypes.c_char_p, P, P, P], S),
         "cv_solver_solve": ([P], S),

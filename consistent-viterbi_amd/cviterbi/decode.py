@@ -263,6 +263,22 @@ def last_superseq_stats(hmm: HMM) -> dict:
                 speculated=out[5], spec_batches=out[6], gathered=out[7], path_waits=out[8])
 
 
+T64_STATS = ("lo_every", "events", "scans", "levels", "overflows", "mismatches", "max_need", "sequences")
+
+
+def last_t64_stats(hmm: HMM) -> dict:
+    """The sparse low-plane resolver's counters of the last f64 trellis decode that has finished
+    on this handle (cv_last_t64_stats): lo_every the call ran with (1: every row full), near-tie
+    events at rows without a low plane, threshold scans and rows descended to resolve them,
+    dense replays (need-set overflows), self-check mismatches, the largest need-set, and the
+    call's sequences."""
+    out = (ctypes.c_int64 * len(T64_STATS))()
+    n = L.lib().cv_last_t64_stats(hmm.handle, out, len(T64_STATS))
+    if n < 0:
+        L.check(L.CV_EINVAL)
+    return {k: int(out[i]) for i, k in enumerate(T64_STATS[:n])}
+
+
 def device_memory() -> dict:
     """Device bytes this process's library holds now and at most (cv_device_memory)."""
     cur, peak = ctypes.c_int64(), ctypes.c_int64()

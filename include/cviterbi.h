@@ -202,6 +202,12 @@ CV_API void cv_hmm_destroy(cv_hmm* h);
  *   t64_cp_w 0            trellis_cp_f64 waves splitting the columns: 1 never, > 1 always (0: up to
  *                         4,096 sequences, NP >= 128); t64_cp_pf 0: its A rows in flight 32 (16)
  *   t64_bt_pf 0           backtrack_f64 rows in flight 2 / 4 / 8 / 16 / 32 (0: by NP)
+ *   t64_lo_every 8        cv_decode_batch[_device], f64 row A0 on log-probability models, 64 < N <= 256:
+ *                         the forward pass writes the low words of its delta rows at every K-th row
+ *                         and the last row only (K <= 16; 1: at every row, the earlier behaviour), and
+ *                         the backtrack recomputes the few exact values a near tie on another row
+ *                         needs (cv_last_t64_stats).  A handle whose call replayed rows densely more
+ *                         than once per 64 sequences (models full of exact ties) runs at 1 from then on
  *   generic_s 0           generic kernels' sequences per workgroup 1 / 2 / 4 (0: by batch)
  *   generic_split 0, generic_split_k 0   1: K threads per state (generic_fwd_split), its K
  *   generic_wide 1, generic_wide_min 0   0: never wide / > 0: wide from this N
@@ -262,6 +268,18 @@ CV_API cv_status cv_decode_batch_device(cv_hmm* h, int64_t nseq, const int64_t* 
                                         const int64_t* offsets_dev, const int32_t* obs_dev,
                                         const cv_opts* opts, int32_t* path_dev, double* score_dev,
                                         uint8_t* status_dev);
+/* Counters of the sparse low-plane backtrack (tuning key t64_lo_every) of the last
+ * cv_decode_batch[_device] call on the f64 trellis that has FINISHED on this handle (they are
+ * copied to the host behind the call's kernels; no synchronisation here -- after cv_decode_batch,
+ * or once the stream of cv_decode_batch_device has been synchronised, they are that call's).
+ * Length-checked: writes min(n, count) words to out and returns count (8 now; later versions may
+ * append words), -1 on a bad argument.  Words: 0 the lo_every the call ran with (1: every row
+ * full -- the key, a decode the sparse rows do not cover, or the handle's guard); 1 near-tie
+ * events at rows without low words; 2 threshold scans and 3 rows descended resolving them;
+ * 4 dense replays (a need-set above 8 states); 5 failed self-checks (always 0; such an event is
+ * replayed densely, so the result is exact all the same, and the handle then stays at 1);
+ * 6 the largest need-set; 7 the call's sequences. */
+CV_API int32_t cv_last_t64_stats(const cv_hmm* h, int64_t* out, int32_t n);
 /* Device timings of the last decode call on this handle (synchronizes its events). */
 CV_API cv_status cv_last_timing(cv_hmm* h, cv_timing* out);
 /* Device timings summed over EVERY decode call on this handle from cv_timing_begin to
