@@ -3,7 +3,8 @@
 TEST INFRASTRUCTURE ONLY: the checker for cv_hmm_mle / cv_hmm_train (GPU), imported by
 tests/ only.  Parity "unpinned" against the Rust binary (it cannot be built here; the
 reference ships no tests or fixtures for fitting); pinned by closed-form cases in
-tests/test_fit.py.
+tests/test_fit.py (one per zero-sum fallback of normalize) and by the 60-digit fixtures
+of tests/golden/make_fit_golden.py.
 
 All arithmetic is f64 in probability space, like the reference; `log_map` is the
 reference's final `log()` (hmm.rs:192-205): x == 0 -> -inf, else x.log(10.0), which Rust
@@ -34,9 +35,14 @@ def log_map(x):
     return out
 
 
-def _normalize(v):
+def _normalize(v, counts=None, which=None):
+    """hmm.rs:274-282 / 306-317.  counts[which] += 1 on the zero-sum branch (fallback_counts)."""
     s = v.sum()
-    return v / s if s != 0.0 else np.full(v.shape, 1.0 / v.size)
+    if s != 0.0:
+        return v / s
+    if counts is not None:
+        counts[which] += 1
+    return np.full(v.shape, 1.0 / v.size)
 
 
 def mle(pi0, a0, b0, offsets, obs, tags):
@@ -72,23 +78,23 @@ def mle(pi0, a0, b0, offsets, obs, tags):
     return log_map(pi), log_map(a), log_map(b)
 
 
-def _alpha(pi, a, b, ob, tg):
+def _alpha(pi, a, b, ob, tg, counts=None):
     n = a.shape[0]
     T = len(ob)
     al = np.zeros((T, n))
     if tg[0] >= 0:
         al[0, tg[0]] = 1.0
     else:
-        al[0] = _normalize(pi * b[:, ob[0]])
+        al[0] = _normalize(pi * b[:, ob[0]], counts, "alpha")
     for t in range(1, T):
         if tg[t] >= 0:
             al[t, tg[t]] = 1.0
         else:
-            al[t] = _normalize((al[t - 1] * b[:, ob[t]]) @ a)  # hmm.rs:93-94, as written
+            al[t] = _normalize((al[t - 1] * b[:, ob[t]]) @ a, counts, "alpha")  # hmm.rs:93-94, as written
     return al
 
 
-def _beta(a, b, ob, tg):
+def _beta(a, b, ob, tg, counts=None):
     n = a.shape[0]
     T = len(ob)
     be = np.zeros((T, n))
@@ -100,13 +106,15 @@ def _beta(a, b, ob, tg):
         if tg[t] >= 0:
             be[t, tg[t]] = 1.0
         else:
-            be[t] = _normalize((be[t + 1] * b[:, ob[t + 1]]) @ a.T)  # hmm.rs:114-116
+            be[t] = _normalize((be[t + 1] * b[:, ob[t + 1]]) @ a.T, counts, "beta")  # hmm.rs:114-116
     return be
 
 
-def train_step(pi, a, b, offsets, obs, tags):
+def train_step(pi, a, b, offsets, obs, tags, counts=None):
     """One EM iteration of hmm.rs:73-178 in probability space; tags -1 = untagged.
-    Returns (new_pi, new_a, new_b, d) with d = sum |new - old| (hmm.rs:172-175)."""
+    Returns (new_pi, new_a, new_b, d) with d = sum |new - old| (hmm.rs:172-175).  A state
+    that no gamma visits has a_den = b_den = 0: its rows of A and B are 0/0 = NaN, as in
+    the reference (hmm.rs:152-154, 170-172).  counts: see fallback_counts."""
     n = a.shape[0]
     V = b.shape[1]
     r = len(offsets) - 1
@@ -119,22 +127,33 @@ def train_step(pi, a, b, offsets, obs, tags):
         lo, hi = int(offsets[s]), int(offsets[s + 1])
         ob = np.asarray(obs[lo:hi], np.int64)
         tg = np.asarray(tags[lo:hi], np.int64)
-        al = _alpha(pi, a, b, ob, tg)
-        be = _beta(a, b, ob, tg)
-        g = np.array([_normalize(al[t] * be[t]) for t in range(len(ob))])  # hmm.rs:124-131
+        al = _alpha(pi, a, b, ob, tg, counts)
+        be = _beta(a, b, ob, tg, counts)
+        g = np.array([_normalize(al[t] * be[t], counts, "gamma") for t in range(len(ob))])  # hmm.rs:124-131
         for t in range(len(ob) - 1):  # hmm.rs:133-143
             m = (b[:, ob[t + 1]] * be[t + 1])[None, :] * al[t][:, None]
-            xi_sum += _normalize((m * a).ravel()).reshape(n, n)
+            xi_sum += _normalize((m * a).ravel(), counts, "xi").reshape(n, n)
         new_pi += g[0]
         a_den += g[:-1].sum(axis=0)
         for t in range(len(ob)):
             new_b[:, ob[t]] += g[t]
         b_den += g.sum(axis=0)
     new_pi /= float(r)
-    new_a = xi_sum / a_den[:, None]
-    new_b = new_b / b_den[:, None]
+    with np.errstate(divide="ignore", invalid="ignore"):  # a never-visited state: x / 0
+        new_a = xi_sum / a_den[:, None]
+        new_b = new_b / b_den[:, None]
     d = np.abs(new_pi - pi).sum() + np.abs(new_a - a).sum() + np.abs(new_b - b).sum()
     return new_pi, new_a, new_b, d
+
+
+def fallback_counts(pi, a, b, offsets, obs, tags):
+    """How often each normalize() of one EM iteration from (pi, a, b) saw a sum of exactly 0
+    and returned the uniform vector (hmm.rs:279, 311): {"alpha", "beta", "gamma", "xi"} ->
+    count.  Tests use it to prove that their inputs reach (or avoid) those branches."""
+    counts = {"alpha": 0, "beta": 0, "gamma": 0, "xi": 0}
+    pi, a, b = (np.asarray(x, np.float64) for x in (pi, a, b))
+    train_step(pi, a, b, offsets, obs, tags, counts)
+    return counts
 
 
 def train(pi0, a0, b0, offsets, obs, tags, max_iter, tol):
