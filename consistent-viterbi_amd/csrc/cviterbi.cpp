@@ -25,9 +25,11 @@
 #include <numeric>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/cviterbi.h"
+#include "batchplan.hpp"
 #include "csp.hpp"
 #include "hostscan.hpp"
 #include "hmm_json.hpp"
@@ -682,17 +684,9 @@ int64_t first_bad(int64_t lo, int64_t hi, P&& bad) {
   return -1;
 }
 
-cv_status check_batch(const cv_hmm* h, int64_t nseq, const int64_t* offsets) {
-  if (nseq < 0) return set_err(CV_EINVAL, "nseq < 0");
-  if (!offsets) return set_err(CV_EINVAL, "offsets is NULL");
-  if (offsets[0] < 0) return set_err(CV_EINVAL, "offsets[0] < 0");
-  for (int64_t s = 0; s < nseq; ++s) {
-    const int64_t T = offsets[s + 1] - offsets[s];
-    if (T < 0) return set_err(CV_EINVAL, "offsets not non-decreasing at %lld", (long long)s);
-    if (T > INT32_MAX) return set_err(CV_EINVAL, "sequence %lld too long", (long long)s);
-  }
-  (void)h;
-  return CV_OK;
+cv_status check_batch(int64_t nseq, const int64_t* offsets) {
+  char msg[64];
+  return cvplan::check_offsets(nseq, offsets, msg) ? CV_OK : set_err(CV_EINVAL, "%s", msg);
 }
 
 hipEvent_t get_event(std::vector<hipEvent_t>& ev, size_t i) {
@@ -704,25 +698,55 @@ hipEvent_t get_event(std::vector<hipEvent_t>& ev, size_t i) {
   return ev[i];
 }
 
-cvk::BacktrackArgs make_bt_args(cv_hmm* h, unsigned char* wsb, const int64_t* offsets_host,
-                                const int64_t* offsets_dev, const int32_t* obs_dev, const int32_t* order_dev,
-                                const std::pair<int64_t, int64_t>& c, int32_t* path_dev, double* score_dev,
-                                uint8_t* status_dev) {
-  cvk::BacktrackArgs ba{};
-  ba.delta = reinterpret_cast<const float*>(wsb);
-  ba.delta_elem_base = offsets_host[c.first];
-  ba.at = h->t_at.as<float>();
-  ba.offsets = offsets_dev;
-  ba.obs = obs_dev;
-  ba.order = order_dev;
-  ba.seq_begin = c.first;
-  ba.seq_end = c.second;
-  ba.nstates = h->N;
-  ba.path = path_dev;
-  ba.score = score_dev;
-  ba.score32 = nullptr;
-  ba.status = status_dev;
-  return ba;
+// ---- scaffolding shared by the device cores (decode_device, posterior_device, kbest_device) ----
+// The host copy of the offsets, checked: the caller's, or fetched from the device into `off_copy`.
+cv_status host_offsets(int64_t nseq, const int64_t*& offsets_host, const int64_t* offsets_dev,
+                       std::vector<int64_t>& off_copy, hipStream_t stream) {
+  if (!offsets_host && nseq >= 0) {
+    off_copy.resize((size_t)nseq + 1);
+    HIP_TRY(hipMemcpyAsync(off_copy.data(), offsets_dev, off_copy.size() * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    offsets_host = off_copy.data();
+  }
+  return check_batch(nseq, offsets_host);
+}
+
+// The longest-first order of a call on its way to the device, through the pinned stage.
+cv_status upload_order(DevBuf& dev, OrderStage& stage, const int32_t* order_host, int64_t nseq, hipStream_t stream,
+                       const int32_t** order_dev) {
+  cv_status st = dev.ensure((size_t)nseq * 4);
+  if (st != CV_OK) return st;
+  int32_t* pin = stage.acquire((size_t)nseq);
+  if (!pin) return set_err(CV_ENOMEM, "pinned staging of %lld order entries failed", (long long)nseq);
+  std::memcpy(pin, order_host, (size_t)nseq * 4);
+  HIP_TRY(hipMemcpyAsync(dev.p, pin, (size_t)nseq * 4, hipMemcpyHostToDevice, stream));
+  HIP_TRY(stage.release(stream));
+  *order_dev = dev.as<int32_t>();
+  return CV_OK;
+}
+
+// The nev timing events of a call, evv[*eb ...]: from 0 (each call overwrites the last), or
+// appended after the calls already timed since cv_timing_begin.  side_ws: the side workspace's
+// own events, no bookkeeping.
+cv_status reserve_events(cv_hmm* h, bool side_ws, size_t nev, size_t* eb) {
+  if (!side_ws && h->acc_on && h->acc_used + nev > kMaxTimedEvents) h->acc_on = false, h->acc_overflow = true;
+  *eb = (!side_ws && h->acc_on) ? h->acc_used : 0;
+  if (!side_ws) h->last_ev_base = *eb;
+  std::vector<hipEvent_t>& evv = side_ws ? h->side.ev : h->ev;
+  for (size_t i = 0; i < nev; ++i)
+    if (!get_event(evv, *eb + i)) return set_err(CV_EDEVICE, "hipEventCreate failed");
+  return CV_OK;
+}
+
+// The end of a core call whose last work is on `stream`: its nev events are kept (cv_timing_begin)
+// and the workspace's ws_done follows it.
+cv_status end_call(cv_hmm* h, bool side_ws, size_t nev, hipStream_t stream) {
+  if (!side_ws && h->acc_on) h->acc_used += nev;
+  hipEvent_t& ws_done = side_ws ? h->side.ws_done : h->ws_done;
+  if (!ws_done) HIP_TRY(hipEventCreateWithFlags(&ws_done, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(ws_done, stream));
+  (side_ws ? h->side.ws_rec : h->ws_rec) = true;
+  return CV_OK;
 }
 
 // Caller-supplied emission scores (cv_decode_emissions*): a dense device array, row e (element
@@ -792,33 +816,53 @@ void t64_stats_sum(const cv_hmm* h, int64_t (&out)[8]) {
   out[7] = (int64_t)(meta[1] & 0xffffffffu);
 }
 
+// The options of decode_device beyond a plain decode; every caller names only what it sets.
+struct DecodeReq {
+  const void* resume_rows = nullptr;  // the constrained decode's resume rows (the kernel's real type)
+  // the handle's second workspace (h->side), no timing / last-call bookkeeping -- a decode
+  // running beside another decode_device call of the same handle on another stream
+  bool side_ws = false;
+  // the parallel CPSolver chain (row-A0 f64 trellis or the f64 generic rows mode): each chunk's
+  // backtrack computes its certificates (or a cp_cert pass reads its rows and paths) -> [nseq][2]
+  double* cp_cert = nullptr;
+  const double* cp_init = nullptr;  // the chain's speculative re-decodes: start offsets in,
+  double* cp_last = nullptr;        // last values out
+  // h->chunk_ev[i] is recorded after chunk i's backtrack (its paths written, before any
+  // certificate pass) and its sequence range [s0, s1) appended
+  std::vector<std::pair<int64_t, int64_t>>* chunks_out = nullptr;
+  // cv_decode_emissions* (f64 only; the caller has checked the options, emissions_opts_ok): the
+  // emissions of every element come from this dense array instead of the handle's b through
+  // obs_dev (ignored, may be null); each chunk's rows are staged beside its delta rows
+  const EmisSrc* emis = nullptr;
+  // cv_decode_batch[_device] only: the f64 trellis may keep sparse low planes (tuning key
+  // t64_lo_every) and records the resolver's counters (cv_last_t64_stats)
+  bool batch_api = false;
+};
+
+// The tables of the generic kernels by real type.
+template <typename REAL>
+struct GenericTables {
+  const REAL *pi, *a, *et, *at;
+};
+template <typename REAL>
+GenericTables<REAL> generic_tables(const cv_hmm* h) {
+  if constexpr (std::is_same_v<REAL, double>)
+    return {h->d_pi64.as<double>(), h->d_a64.as<double>(), h->d_et64.as<double>(), h->d_at64.as<double>()};
+  else
+    return {h->d_pi32.as<float>(), h->d_a32.as<float>(), h->d_et32.as<float>(), h->d_at32.as<float>()};
+}
+
 // Core device-side decode.  All pointers are device pointers except offsets_host.
-// emis (cv_decode_emissions*, f64 only): the emissions of every element come from this dense
-// array instead of the handle's b through obs_dev (ignored, may be null): each chunk's rows are
-// staged beside its delta rows (stage_emissions) and the same kernels decode them; the caller
-// has checked the options (emissions_opts_ok: f64, not the f32 trellis kernel).
 cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, const int64_t* offsets_dev,
                         const int32_t* obs_dev, const cv_opts& o, int32_t* path_dev, double* score_dev,
-                        uint8_t* status_dev, hipStream_t stream, const void* resume_rows = nullptr,
-                        bool side_ws = false, double* cp_cert = nullptr, const double* cp_init = nullptr,
-                        double* cp_last = nullptr,
-                        std::vector<std::pair<int64_t, int64_t>>* chunks_out = nullptr,
-                        const EmisSrc* emis = nullptr, bool batch_api = false) {
-  // batch_api (cv_decode_batch[_device] only): the f64 trellis may keep sparse low planes
-  // (tuning key t64_lo_every) and records the resolver's counters (cv_last_t64_stats)
-  // cp_cert (the parallel CPSolver chain, row-A0 f64 trellis only): each chunk's backtrack
-  // computes its certificates (or cp_cert_f64 reads the chunk's rows and paths) -> [nseq][2];
-  // chunks_out: h->chunk_ev[i] is recorded after chunk i's backtrack (its paths written,
-  // before any certificate pass) and its sequence range [s0, s1) appended
-  // side_ws: the handle's second workspace (h->side), no timing / last-call bookkeeping -- a
-  // decode running beside another decode_device call of the same handle on another stream
+                        uint8_t* status_dev, hipStream_t stream, const DecodeReq& rq = DecodeReq{}) {
+  const bool side_ws = rq.side_ws;
+  const EmisSrc* const emis = rq.emis;
   DevBuf& w_main = side_ws ? h->side.main : h->ws_main;
   DevBuf& w_last = side_ws ? h->side.last : h->ws_last;
-  DevBuf& w_order = side_ws ? h->side.order : h->ws_order;
   std::vector<int32_t>& order_host = side_ws ? h->side.order_host : h->order_host;
-  OrderStage& order_pin = side_ws ? h->side.order_pin : h->order_pin;
-  hipEvent_t& ws_done = side_ws ? h->side.ws_done : h->ws_done;
-  bool& ws_rec = side_ws ? h->side.ws_rec : h->ws_rec;
+  const bool ws_rec = side_ws ? h->side.ws_rec : h->ws_rec;
+  const hipEvent_t ws_done = side_ws ? h->side.ws_done : h->ws_done;
   std::vector<hipEvent_t>& evv = side_ws ? h->side.ev : h->ev;
   int64_t launches_done = 0;
   if (o.dtype != CV_DTYPE_F32 && o.dtype != CV_DTYPE_F64) return set_err(CV_EINVAL, "bad dtype %d", o.dtype);
@@ -851,10 +895,10 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
   const bool t512_pick = h->tuning.t64_512 == 1 || h->N >= 384 || nseq >= 8192;
   const bool small_ok = (o.assoc == CV_ASSOC_VITERBI || o.assoc == CV_ASSOC_DECODE || o.assoc == CV_ASSOC_CP ||
                          o.assoc == CV_ASSOC_DP) &&
-                        (!(o.forced || resume_rows) || o.assoc == CV_ASSOC_VITERBI) && cvk::t64_padded_states(h->N) != 0;
+                        (!(o.forced || rq.resume_rows) || o.assoc == CV_ASSOC_VITERBI) && cvk::t64_padded_states(h->N) != 0;
   const bool big_ok = cvk::t64_support_states(h->N) >= 512 &&
                       (o.assoc == CV_ASSOC_VITERBI || ((o.assoc == CV_ASSOC_DECODE || o.assoc == CV_ASSOC_DP) && !o.forced)) &&
-                      !resume_rows && !cp_init && !cp_last;
+                      !rq.resume_rows && !rq.cp_init && !rq.cp_last;
   const bool big_pick = cvk::t64_batch_states(h->N) >= 512 && (t512_pick || h->N > 512);
   const bool t64_ok = o.dtype == CV_DTYPE_F64 && (small_ok || big_ok);
   if (o.kernel == CV_KERNEL_TRELLIS_F64 && !t64_ok)
@@ -874,16 +918,10 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
   const bool gen_global =
       !use_trellis && !use_t64 &&
       (h->N > cvk::generic_max_states(o.dtype == CV_DTYPE_F64 ? 8 : 4) ||
-       (!cp_cert && cvk::generic_wide(h->N, o.dtype == CV_DTYPE_F64 ? 8 : 4, nseq, o.assoc == CV_ASSOC_CP)));
+       (!rq.cp_cert && cvk::generic_wide(h->N, o.dtype == CV_DTYPE_F64 ? 8 : 4, nseq, o.assoc == CV_ASSOC_CP)));
 
   std::vector<int64_t> off_copy;
-  if (!offsets_host) {
-    off_copy.resize((size_t)nseq + 1);
-    HIP_TRY(hipMemcpyAsync(off_copy.data(), offsets_dev, off_copy.size() * 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    offsets_host = off_copy.data();
-  }
-  cv_status st = check_batch(h, nseq, offsets_host);
+  cv_status st = host_offsets(nseq, offsets_host, offsets_dev, off_copy, stream);
   if (st != CV_OK) return st;
 
   const bool need_f64 = (o.rescore_f64 && o.dtype == CV_DTYPE_F32) || o.dtype == CV_DTYPE_F64;
@@ -924,7 +962,7 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
   // (profiles/r04_large_n.txt)
   const bool gen_rows =
       !use_trellis && !use_t64 && !gen_global && o.assoc != CV_ASSOC_CP && h->tuning.generic_rows != 0;
-  if (cp_cert && !use_t64 && !(gen_rows && o.dtype == CV_DTYPE_F64))
+  if (rq.cp_cert && !use_t64 && !(gen_rows && o.dtype == CV_DTYPE_F64))
     return set_err(CV_EUNSUPPORTED, "chain certificates need the f64 trellis or the generic kernels' rows mode");
   if (gen_rows && (st = o.dtype == CV_DTYPE_F64 ? ensure_at64(h) : ensure_at32(h)) != CV_OK) return st;
   const uint64_t per_elem = use_trellis ? (uint64_t)(wave ? h->npw : h->np) * 4
@@ -937,7 +975,6 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
   const int estride = use_t64 ? h->np64 : h->N;
   const uint64_t rows_per_elem = per_elem;
   const uint64_t stage_per_elem = emis ? (uint64_t)estride * 8 + 4 : 0;
-  const uint64_t total_elems = (uint64_t)(offsets_host[nseq] - offsets_host[0]);
   // Chunks (contiguous in the original order) are pipelined over two streams: the forward
   // pass of chunk k+1 runs while chunk k backtracks, out of a double-buffered workspace.
   // At least ~2,048 sequences per chunk (8 per CU), at most 8 chunks unless the
@@ -954,47 +991,12 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
     const int v = h->tuning.max_chunks;
     return (uint64_t)(v >= 1 && v <= 64 ? v : 8);
   }();
-  std::vector<std::pair<int64_t, int64_t>> chunks;
+  std::vector<cvplan::Chunk> chunks;
   // the batch split under the cap at per_elem_all workspace bytes per element
   auto split = [&](const uint64_t per_elem_all) {
-    chunks.clear();
-    const uint64_t half_cap = std::max<uint64_t>(serial ? cap : cap / 2, per_elem_all);
-    uint64_t nchunks = std::max<uint64_t>(1, (total_elems * per_elem_all + half_cap - 1) / half_cap);
-    if (!serial) nchunks = std::max<uint64_t>(nchunks, std::min<uint64_t>(max_chunks, (uint64_t)(nseq / 2048)));
-    const uint64_t target = std::max<uint64_t>(1, (total_elems + nchunks - 1) / nchunks);
-    const uint64_t elem_cap = std::max<uint64_t>(half_cap / per_elem_all, 1);
-    {
-      int64_t s0 = 0;
-      while (s0 < nseq) {
-        int64_t s1 = s0;
-        uint64_t elems = 0;
-        while (s1 < nseq) {
-          const uint64_t T = (uint64_t)(offsets_host[s1 + 1] - offsets_host[s1]);
-          if (s1 > s0 && (elems + T > elem_cap || elems + T > target)) break;
-          elems += T;
-          ++s1;
-          if (s1 - s0 >= (1 << 30)) break;
-        }
-        chunks.emplace_back(s0, s1);
-        s0 = s1;
-      }
-    }
-    {
-      // Equal lengths: whole rounds of workgroups (group x CUs sequences) per chunk, so only
-      // the last chunk ends on a partly filled round (a chunk's launch waits for the last).
-      const int64_t T0c = offsets_host[1] - offsets_host[0];
-      bool uniform = T0c > 0;
-      for (int64_t s = 1; s < nseq && uniform; ++s) uniform = (offsets_host[s + 1] - offsets_host[s]) == T0c;
-      const int64_t unit = (use_t64 ? 64 : group) * (int64_t)std::max(h->cus, 1);
-      if (uniform && chunks.size() > 1) {
-        const int64_t cap_seqs = std::max<int64_t>((int64_t)(elem_cap / (uint64_t)T0c), 1);
-        int64_t per = (nseq + (int64_t)chunks.size() - 1) / (int64_t)chunks.size();
-        per = ((per + unit - 1) / unit) * unit;
-        if (per > cap_seqs) per = cap_seqs >= unit ? (cap_seqs / unit) * unit : cap_seqs;
-        chunks.clear();
-        for (int64_t s0 = 0; s0 < nseq; s0 += per) chunks.emplace_back(s0, std::min(nseq, s0 + per));
-      }
-    }
+    cvplan::split_pipelined(offsets_host, nseq,
+                            {per_elem_all, cap, serial, max_chunks, (use_t64 ? 64 : group) * (int64_t)std::max(h->cus, 1)},
+                            chunks);
   };
   split(rows_per_elem + stage_per_elem);
   // Tuning key emis_overlap = 1 (bit-identical; off by default): dense emissions on the f64
@@ -1006,16 +1008,11 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
   // split decides: 57.0 vs 39.8 ms and 38.8 vs 49.3 ms at two caps (profiles/emissions_bench.txt)
   const bool eov = emis && use_t64 && !side_ws && chunks.size() > 1 && h->tuning.emis_overlap != 0;
   if (eov) split(rows_per_elem + 2 * stage_per_elem);
-  uint64_t max_elems = 0;
-  int64_t max_seqs = 0;
-  bool varlen = false;
-  for (auto& c : chunks) {
-    max_elems = std::max<uint64_t>(max_elems, (uint64_t)(offsets_host[c.second] - offsets_host[c.first]));
-    max_seqs = std::max<int64_t>(max_seqs, c.second - c.first);
-  }
+  const cvplan::Shares largest = cvplan::measure(offsets_host, chunks);
+  const uint64_t max_elems = largest.max_elems;
+  const int64_t max_seqs = largest.max_seqs;
   const int nbuf = (chunks.size() > 1 && !serial) ? 2 : 1;
-  const int64_t T0 = offsets_host[1] - offsets_host[0];
-  for (int64_t s = 1; s < nseq && !varlen; ++s) varlen = (offsets_host[s + 1] - offsets_host[s]) != T0;
+  const bool varlen = cvplan::varlen(offsets_host, nseq);
   const size_t rows_bytes = ((std::max<uint64_t>(max_elems, 1) * rows_per_elem + 255) / 256) * 256;
   const size_t stage_bytes = emis ? ((std::max<uint64_t>(max_elems, 1) * estride * 8 + 255) / 256) * 256 : 0;
   const size_t idx_bytes = emis ? ((std::max<uint64_t>(max_elems, 1) * 4 + 255) / 256) * 256 : 0;
@@ -1044,53 +1041,17 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
     // longest-first schedule inside each chunk so the tail of the grid is short sequences;
     // with pairing, equal-length neighbours are paired first and leftovers go last
     order_host.resize((size_t)nseq);
-    std::vector<int32_t> tail;
-    for (size_t ci = 0; ci < chunks.size(); ++ci) {
-      const auto& c = chunks[ci];
-      auto b = order_host.begin() + c.first, e = order_host.begin() + c.second;
-      auto len = [&](int32_t x) { return offsets_host[x + 1] - offsets_host[x]; };
-      // stable longest-first: a counting sort on the lengths (a comparison sort of 16,384
-      // sequences cost ~1 ms of host time per call), a stable sort for very long lengths
-      int64_t maxlen = 0;
-      for (int64_t x = c.first; x < c.second; ++x) maxlen = std::max<int64_t>(maxlen, len((int32_t)x));
-      if (maxlen <= 4 * (c.second - c.first) + (1 << 16)) {
-        std::vector<int64_t>& pos = h->sort_pos;
-        pos.assign((size_t)maxlen + 2, 0);
-        for (int64_t x = c.first; x < c.second; ++x) ++pos[(size_t)(maxlen - len((int32_t)x)) + 1];
-        for (size_t k = 1; k < pos.size(); ++k) pos[k] += pos[k - 1];
-        for (int64_t x = c.first; x < c.second; ++x) b[pos[(size_t)(maxlen - len((int32_t)x))]++] = (int32_t)x;
-      } else {
-        std::iota(b, e, (int32_t)c.first);
-        std::stable_sort(b, e, [&](int32_t x, int32_t y) { return len(x) > len(y); });
-      }
-      if (!pairing) continue;
-      tail.clear();
-      auto out = b;
-      for (auto it = b; it != e;) {
-        if (it + 1 != e && len(*it) == len(*(it + 1))) {
-          *out++ = *it++;
-          *out++ = *it++;
-        } else {
-          tail.push_back(*it++);
-        }
-      }
-      npair[ci] = (out - b) / 2;
-      std::copy(tail.begin(), tail.end(), out);
-    }
-    if ((st = w_order.ensure((size_t)nseq * 4)) != CV_OK) return st;
-    int32_t* pin = order_pin.acquire((size_t)nseq);
-    if (!pin) return set_err(CV_ENOMEM, "pinned staging of %lld order entries failed", (long long)nseq);
-    std::memcpy(pin, order_host.data(), (size_t)nseq * 4);
-    HIP_TRY(hipMemcpyAsync(w_order.p, pin, (size_t)nseq * 4, hipMemcpyHostToDevice, stream));
-    HIP_TRY(order_pin.release(stream));
-    order_dev = w_order.as<int32_t>();
+    cvplan::longest_first(offsets_host, chunks, order_host.data(), pairing ? npair.data() : nullptr, h->sort_pos);
+    if ((st = upload_order(side_ws ? h->side.order : h->ws_order, side_ws ? h->side.order_pin : h->order_pin,
+                           order_host.data(), nseq, stream, &order_dev)) != CV_OK)
+      return st;
   }
 
   // Sparse low planes (trellis64.h row contract): only where the forward and the backtrack are
   // the plain NONPOS row-A0 pair and nothing else reads the rows -- no forced states, resume rows,
   // chain certificates or chunk events, dense emissions, DPSolver / viterbi::decode rows -- at
   // NP = 128 / 192 / 256.  Every other decode writes and reads full rows.
-  const bool t64_stats_on = batch_api && use_t64 && !t64cp && !side_ws;
+  const bool t64_stats_on = rq.batch_api && use_t64 && !t64cp && !side_ws;
   int lo_every = 1;
   if (t64_stats_on) {
     constexpr size_t kStatBytes = (size_t)(cvk::kT64StatSlots + 1) * cvk::kT64StatWords * 8;
@@ -1102,8 +1063,8 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
     int64_t last[8];
     t64_stats_sum(h, last);  // the previous call's counters if it has finished (no wait: else older ones)
     if (last[0] > 1 && (last[4] * 64 > last[7] || last[5] > 0)) h->t64_lo_off = true;
-    const bool plain_pair = o.assoc == CV_ASSOC_VITERBI && !o.forced && !resume_rows && !cp_cert && !cp_init &&
-                            !cp_last && !chunks_out && !emis && h->t64_nonpos &&
+    const bool plain_pair = o.assoc == CV_ASSOC_VITERBI && !o.forced && !rq.resume_rows && !rq.cp_cert && !rq.cp_init &&
+                            !rq.cp_last && !rq.chunks_out && !emis && h->t64_nonpos &&
                             (h->np64 == 128 || h->np64 == 192 || h->np64 == 256);
     if (plain_pair && !h->t64_lo_off)
       lo_every = std::min(std::max(h->tuning.t64_lo_every, 1), cvk::kT64LoEveryMax);
@@ -1115,15 +1076,32 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
 
   hipStream_t bts = serial ? stream : h->bt_stream;
   const size_t nev = 4 * chunks.size();
-  // events of this call: from 0 (each call overwrites the last), or appended after the calls
-  // already timed since cv_timing_begin
-  if (!side_ws && h->acc_on && h->acc_used + nev > kMaxTimedEvents) h->acc_on = false, h->acc_overflow = true;
-  const size_t eb = (!side_ws && h->acc_on) ? h->acc_used : 0;
-  if (!side_ws) h->last_ev_base = eb;
-  for (size_t i = 0; i < nev; ++i)
-    if (!get_event(evv, eb + i)) return set_err(CV_EDEVICE, "hipEventCreate failed");
+  size_t eb;
+  if ((st = reserve_events(h, side_ws, nev, &eb)) != CV_OK) return st;
+  // The chunk the loop below is at -- its sequences, its rows and last rows in the workspace, its
+  // staged dense emissions -- and the kernel arguments of that chunk
+  cvplan::Chunk c;
+  unsigned char *wsb = nullptr, *lrb = nullptr;
+  EmisView ev{};
+  auto trellis_bt_args = [&] {
+    cvk::BacktrackArgs ba{};
+    ba.delta = reinterpret_cast<const float*>(wsb);
+    ba.delta_elem_base = offsets_host[c.first];
+    ba.at = h->t_at.as<float>();
+    ba.offsets = offsets_dev;
+    ba.obs = obs_dev;
+    ba.order = order_dev;
+    ba.seq_begin = c.first;
+    ba.seq_end = c.second;
+    ba.nstates = h->N;
+    ba.path = path_dev;
+    ba.score = score_dev;
+    ba.score32 = nullptr;
+    ba.status = status_dev;
+    return ba;
+  };
   // the f64 trellis backtrack of one chunk (backtrack_f64, or fused into the N <= 64 forward)
-  auto t64_bt_args = [&](const std::pair<int64_t, int64_t>& c, unsigned char* wsb) {
+  auto t64_bt_args = [&] {
     cvk::T64BtArgs ba{};
     ba.delta = reinterpret_cast<const double*>(wsb);
     ba.delta_elem_base = offsets_host[c.first];
@@ -1147,16 +1125,106 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
     ba.stats = h->t64_stats.as<unsigned long long>();
     return ba;
   };
+  auto generic_fwd_args = [&](auto real) {  // real: 0.0 / 0.0f, the kernel's type
+    using REAL = decltype(real);
+    const GenericTables<REAL> tab = generic_tables<REAL>(h);
+    cvk::GenericFwdArgs<REAL> fa{};
+    fa.a = tab.a;
+    fa.pi = tab.pi;
+    fa.et = tab.et;
+    fa.offsets = offsets_dev;
+    fa.obs = obs_dev;
+    fa.order = order_dev;
+    fa.seq_begin = c.first;
+    fa.nstates = h->N;
+    fa.nobs = (int)h->V;
+    fa.assoc = o.assoc;
+    fa.psi = reinterpret_cast<uint16_t*>(wsb);
+    fa.psi_elem_base = offsets_host[c.first];
+    fa.last_row = reinterpret_cast<REAL*>(lrb);
+    fa.status = status_dev;
+    fa.forced = o.forced;
+    if constexpr (std::is_same_v<REAL, double>) {
+      fa.cp_init = rq.cp_init;  // the parallel chain's speculative re-decodes (N > 256)
+      fa.cp_last = rq.cp_last;
+      if (emis) fa.et = ev.et, fa.obs = ev.obs, fa.nobs = ev.nobs;
+    }
+    if (gen_rows) fa.rows = reinterpret_cast<REAL*>(wsb);
+    if (gen_global) {  // wide: the chunk's rows after its last rows, one launch per step
+      fa.grows = reinterpret_cast<REAL*>(lrb) + (size_t)max_seqs * h->N;
+      for (int64_t sq = c.first; sq < c.second; ++sq)
+        fa.wide_steps = std::max<int64_t>(fa.wide_steps, offsets_host[sq + 1] - offsets_host[sq]);
+    }
+    return fa;
+  };
+  auto generic_bt_args = [&](auto real) {
+    using REAL = decltype(real);
+    const GenericTables<REAL> tab = generic_tables<REAL>(h);
+    cvk::GenericBtArgs<REAL> ba{};
+    ba.psi = reinterpret_cast<const uint16_t*>(wsb);
+    ba.psi_elem_base = offsets_host[c.first];
+    ba.last_row = reinterpret_cast<const REAL*>(lrb);
+    ba.offsets = offsets_dev;
+    ba.order = order_dev;
+    ba.seq_begin = c.first;
+    ba.seq_end = c.second;
+    ba.nstates = h->N;
+    ba.path = path_dev;
+    ba.score = score_dev;
+    ba.status = status_dev;
+    ba.obs = obs_dev;
+    // the f64 kernel's own score is already reference numerics
+    ba.rescore_f64 = (std::is_same_v<REAL, float> && o.rescore_f64) ? 1 : 0;
+    ba.decode_bt = o.assoc == CV_ASSOC_DECODE ? 1 : 0;
+    ba.pi64 = h->d_pi64.as<double>();
+    ba.a64 = h->d_a64.as<double>();
+    ba.et64 = h->d_et64.as<double>();
+    if (gen_rows) {
+      ba.rows = reinterpret_cast<const REAL*>(wsb);
+      ba.at = tab.at;
+      ba.et = tab.et;
+      ba.assoc = o.assoc;
+      ba.nobs = (int)h->V;
+    }
+    if constexpr (std::is_same_v<REAL, double>)
+      if (emis) ba.et64 = ba.et = ev.et, ba.obs = ev.obs, ba.nobs = ev.nobs;
+    return ba;
+  };
+  // the chain's certificate pass over the chunk's f64 rows and paths, by the a^T table of its kernel
+  auto cp_cert_args = [&](const double* at) {
+    cvk::CpCert64Args ca{};
+    ca.delta = reinterpret_cast<const double*>(wsb);
+    ca.delta_elem_base = offsets_host[c.first];
+    ca.at = at;
+    ca.offsets = offsets_dev;
+    ca.order = order_dev;
+    ca.seq_begin = c.first;
+    ca.seq_end = c.second;
+    ca.nstates = h->N;
+    ca.path = path_dev;
+    ca.status = status_dev;
+    ca.out = rq.cp_cert;
+    return ca;
+  };
+  // DecodeReq::chunks_out: the chunk's paths are written at this point of `bts`
+  auto note_chunk_done = [&]() -> cv_status {
+    if (!rq.chunks_out) return CV_OK;
+    hipEvent_t ce = get_event(h->chunk_ev, rq.chunks_out->size());
+    if (!ce) return set_err(CV_EDEVICE, "hipEventCreate failed");
+    HIP_TRY(hipEventRecord(ce, bts));
+    rq.chunks_out->push_back(c);
+    return CV_OK;
+  };
   for (size_t ci = 0; ci < chunks.size(); ++ci) {
-    const auto& c = chunks[ci];
+    c = chunks[ci];
     const int64_t n = c.second - c.first;
     const int buf = nbuf == 2 ? (int)(ci % 2) : 0;
-    unsigned char* wsb = w_main.as<unsigned char>() + buf * buf_bytes;
-    unsigned char* lrb = w_last.as<unsigned char>() + buf * last_bytes;
+    wsb = w_main.as<unsigned char>() + buf * buf_bytes;
+    lrb = w_last.as<unsigned char>() + buf * last_bytes;
     hipEvent_t f0 = evv[eb + 4 * ci], f1 = evv[eb + 4 * ci + 1], b0 = evv[eb + 4 * ci + 2], b1 = evv[eb + 4 * ci + 3];
     if (!serial && ci >= 2) HIP_TRY(hipStreamWaitEvent(stream, evv[eb + 4 * (ci - 2) + 3], 0));  // buffer reuse
     HIP_TRY(hipEventRecord(f0, stream));
-    EmisView ev{};  // dense emissions: this chunk's staged rows replace (table, obs_dev, V) below
+    ev = EmisView{};  // dense emissions: this chunk's staged rows replace (table, obs_dev, V) below
     auto stage = [&](size_t k, hipStream_t s, EmisView* out) {
       unsigned char* sb = wsb + rows_bytes + (eov ? k % 2 : 0) * (stage_bytes + idx_bytes);
       return stage_emissions(h, *emis, offsets_host, offsets_dev, chunks[k], estride, reinterpret_cast<double*>(sb),
@@ -1184,13 +1252,12 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
       fa.status = status_dev;
       fa.nobs = (int)h->V;
       fa.forced = o.forced;
-      fa.resume_rows = static_cast<const float*>(resume_rows);
+      fa.resume_rows = static_cast<const float*>(rq.resume_rows);
       if (wave) {
         fa.a_img = h->w_arm.as<float>();
         fa.pi = h->w_pi.as<float>();
         fa.et = h->w_et.as<float>();
-        cvk::BacktrackArgs ba =
-            make_bt_args(h, wsb, offsets_host, offsets_dev, obs_dev, order_dev, c, path_dev, score_dev, status_dev);
+        cvk::BacktrackArgs ba = trellis_bt_args();
         ba.at = h->w_at.as<float>();
         err = cvk::launch_trellis_wave(h->npw, fa, ba, n, stream);
       } else {
@@ -1218,7 +1285,7 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
       fa.zero_init = o.assoc == CV_ASSOC_DECODE ? 1 : 0;
       fa.dp_assoc = o.assoc == CV_ASSOC_DP ? 1 : 0;
       fa.forced = o.forced;
-      fa.resume_rows = static_cast<const double*>(resume_rows);
+      fa.resume_rows = static_cast<const double*>(rq.resume_rows);
       fa.lo_every = lo_every;
       if (emis) fa.et = ev.et, fa.obs = ev.obs, fa.nobs = ev.nobs;
       const int spw = cvk::t64_seqs_per_wave(n, h->cus, h->np64);
@@ -1241,64 +1308,17 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
         fa.nstates = h->N;
         fa.psi = reinterpret_cast<uint16_t*>(wsb);
         fa.last_row = reinterpret_cast<double*>(lrb);
-        fa.cp_init = cp_init;  // the parallel chain's speculative re-decodes (start offsets)
-        fa.cp_last = cp_last;
+        fa.cp_init = rq.cp_init;  // the parallel chain's speculative re-decodes (start offsets)
+        fa.cp_last = rq.cp_last;
         err = cvk::launch_t64_cp_fwd(h->np64, spw, fa, n, stream);
       } else {
         fa.nstates = h->N;  // the N <= 48 one-wave kernel
         err = cvk::launch_t64_fwd(h->np64, spw, fa, n, stream);
       }
     } else if (o.dtype == CV_DTYPE_F64) {
-      cvk::GenericFwdArgs<double> fa{};
-      fa.a = h->d_a64.as<double>();
-      fa.pi = h->d_pi64.as<double>();
-      fa.et = h->d_et64.as<double>();
-      fa.offsets = offsets_dev;
-      fa.obs = obs_dev;
-      fa.order = order_dev;
-      fa.seq_begin = c.first;
-      fa.nstates = h->N;
-      fa.nobs = (int)h->V;
-      fa.assoc = o.assoc;
-      fa.psi = reinterpret_cast<uint16_t*>(wsb);
-      fa.psi_elem_base = offsets_host[c.first];
-      fa.last_row = reinterpret_cast<double*>(lrb);
-      fa.status = status_dev;
-      fa.forced = o.forced;
-      fa.cp_init = cp_init;  // the parallel chain's speculative re-decodes (N > 256)
-      fa.cp_last = cp_last;
-      if (emis) fa.et = ev.et, fa.obs = ev.obs, fa.nobs = ev.nobs;
-      if (gen_rows) fa.rows = reinterpret_cast<double*>(wsb);
-      if (gen_global) {  // wide: the chunk's rows after its last rows, one launch per step
-        fa.grows = reinterpret_cast<double*>(lrb) + (size_t)max_seqs * h->N;
-        for (int64_t sq = c.first; sq < c.second; ++sq)
-          fa.wide_steps = std::max<int64_t>(fa.wide_steps, offsets_host[sq + 1] - offsets_host[sq]);
-      }
-      err = cvk::launch_generic_fwd<double>(fa, n, stream);
+      err = cvk::launch_generic_fwd<double>(generic_fwd_args(0.0), n, stream);
     } else {
-      cvk::GenericFwdArgs<float> fa{};
-      fa.a = h->d_a32.as<float>();
-      fa.pi = h->d_pi32.as<float>();
-      fa.et = h->d_et32.as<float>();
-      fa.offsets = offsets_dev;
-      fa.obs = obs_dev;
-      fa.order = order_dev;
-      fa.seq_begin = c.first;
-      fa.nstates = h->N;
-      fa.nobs = (int)h->V;
-      fa.assoc = o.assoc;
-      fa.psi = reinterpret_cast<uint16_t*>(wsb);
-      fa.psi_elem_base = offsets_host[c.first];
-      fa.last_row = reinterpret_cast<float*>(lrb);
-      fa.status = status_dev;
-      fa.forced = o.forced;
-      if (gen_rows) fa.rows = reinterpret_cast<float*>(wsb);
-      if (gen_global) {  // wide: the chunk's rows after its last rows, one launch per step
-        fa.grows = reinterpret_cast<float*>(lrb) + (size_t)max_seqs * h->N;
-        for (int64_t sq = c.first; sq < c.second; ++sq)
-          fa.wide_steps = std::max<int64_t>(fa.wide_steps, offsets_host[sq + 1] - offsets_host[sq]);
-      }
-      err = cvk::launch_generic_fwd<float>(fa, n, stream);
+      err = cvk::launch_generic_fwd<float>(generic_fwd_args(0.0f), n, stream);
     }
     if (err != hipSuccess) return set_err(CV_EDEVICE, "forward launch failed: %s", hipGetErrorString(err));
     HIP_TRY(hipEventRecord(f1, stream));
@@ -1312,8 +1332,7 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
     if (!serial) HIP_TRY(hipStreamWaitEvent(bts, f1, 0));
     HIP_TRY(hipEventRecord(b0, bts));
     if (use_trellis) {
-      const cvk::BacktrackArgs ba =
-          make_bt_args(h, wsb, offsets_host, offsets_dev, obs_dev, order_dev, c, path_dev, score_dev, status_dev);
+      const cvk::BacktrackArgs ba = trellis_bt_args();
       // overlap mode: at most ONE backtrack workgroup (one 64-VGPR wave per SIMD) per CU, so
       // the next forward workgroup (4 waves x 104 VGPRs per SIMD) always
       // finds its registers free: reserve 100 KiB of LDS (2 x 100 > 160 KiB)
@@ -1337,113 +1356,28 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
         err = cvk::launch_rescore_f64(ra, n, bts, reserve);
       }
     } else if (use_t64 && !t64cp) {
-      cvk::T64BtArgs ba = t64_bt_args(c, wsb);
+      cvk::T64BtArgs ba = t64_bt_args();
       if (emis) ba.et = ev.et, ba.obs = ev.obs;
       // the parallel chain's certificates inside the backtrack (NONPOS row A0, NP <= 256): no
       // second pass over every row (tuning key chain_cert_fused = 0: the cp_cert_f64 pass)
-      const bool fused_cert = cp_cert && ba.at32 && !ba.dp_assoc && !ba.decode_bt && h->np64 <= 256 &&
+      const bool fused_cert = rq.cp_cert && ba.at32 && !ba.dp_assoc && !ba.decode_bt && h->np64 <= 256 &&
                               h->tuning.chain_cert_fused != 0;
       if (fused_cert) {
-        ba.cert = cp_cert;
+        ba.cert = rq.cp_cert;
         ba.rho_cap = h->cert_rho_cap;
       }
       err = cvk::launch_t64_bt(h->np64, ba, n, bts);
-      if (err == hipSuccess && chunks_out) {
-        hipEvent_t ce = get_event(h->chunk_ev, chunks_out->size());
-        if (!ce) return set_err(CV_EDEVICE, "hipEventCreate failed");
-        HIP_TRY(hipEventRecord(ce, bts));
-        chunks_out->push_back(c);
-      }
-      if (err == hipSuccess && cp_cert && !fused_cert) {
-        cvk::CpCert64Args ca{};
-        ca.delta = reinterpret_cast<const double*>(wsb);
-        ca.delta_elem_base = offsets_host[c.first];
-        ca.at = h->q_at.as<double>();
-        ca.offsets = offsets_dev;
-        ca.order = order_dev;
-        ca.seq_begin = c.first;
-        ca.seq_end = c.second;
-        ca.nstates = h->N;
-        ca.path = path_dev;
-        ca.status = status_dev;
-        ca.out = cp_cert;
-        err = cvk::launch_cp_cert(h->np64, ca, bts);
-      }
+      if (err == hipSuccess && (st = note_chunk_done()) != CV_OK) return st;
+      if (err == hipSuccess && rq.cp_cert && !fused_cert)
+        err = cvk::launch_cp_cert(h->np64, cp_cert_args(h->q_at.as<double>()), bts);
     } else if (o.dtype == CV_DTYPE_F64) {
-      cvk::GenericBtArgs<double> ba{};
-      ba.psi = reinterpret_cast<const uint16_t*>(wsb);
-      ba.psi_elem_base = offsets_host[c.first];
-      ba.last_row = reinterpret_cast<const double*>(lrb);
-      ba.offsets = offsets_dev;
-      ba.order = order_dev;
-      ba.seq_begin = c.first;
-      ba.seq_end = c.second;
-      ba.nstates = h->N;
-      ba.path = path_dev;
-      ba.score = score_dev;
-      ba.status = status_dev;
-      ba.obs = obs_dev;
-      ba.rescore_f64 = 0;  // the f64 kernel's own score is already reference numerics
-      ba.decode_bt = o.assoc == CV_ASSOC_DECODE ? 1 : 0;
-      ba.pi64 = h->d_pi64.as<double>();
-      ba.a64 = h->d_a64.as<double>();
-      ba.et64 = h->d_et64.as<double>();
-      if (gen_rows) {
-        ba.rows = reinterpret_cast<const double*>(wsb);
-        ba.at = h->d_at64.as<double>();
-        ba.et = h->d_et64.as<double>();
-        ba.assoc = o.assoc;
-        ba.nobs = (int)h->V;
-      }
-      if (emis) ba.et64 = ba.et = ev.et, ba.obs = ev.obs, ba.nobs = ev.nobs;
+      const cvk::GenericBtArgs<double> ba = generic_bt_args(0.0);
       err = gen_rows ? cvk::launch_generic_bt_rows<double>(ba, n, bts) : cvk::launch_generic_bt<double>(ba, n, bts);
-      if (err == hipSuccess && chunks_out) {
-        hipEvent_t ce = get_event(h->chunk_ev, chunks_out->size());
-        if (!ce) return set_err(CV_EDEVICE, "hipEventCreate failed");
-        HIP_TRY(hipEventRecord(ce, bts));
-        chunks_out->push_back(c);
-      }
-      if (err == hipSuccess && cp_cert) {  // the parallel chain (N > 256): certificates over the plain rows
-        cvk::CpCert64Args ca{};
-        ca.delta = reinterpret_cast<const double*>(wsb);
-        ca.delta_elem_base = offsets_host[c.first];
-        ca.at = h->d_at64.as<double>();
-        ca.offsets = offsets_dev;
-        ca.order = order_dev;
-        ca.seq_begin = c.first;
-        ca.seq_end = c.second;
-        ca.nstates = h->N;
-        ca.path = path_dev;
-        ca.status = status_dev;
-        ca.out = cp_cert;
-        err = cvk::launch_cp_cert_plain(ca, bts);
-      }
+      if (err == hipSuccess && (st = note_chunk_done()) != CV_OK) return st;
+      if (err == hipSuccess && rq.cp_cert)  // the parallel chain (N > 256): certificates over the plain rows
+        err = cvk::launch_cp_cert_plain(cp_cert_args(h->d_at64.as<double>()), bts);
     } else {
-      cvk::GenericBtArgs<float> ba{};
-      ba.psi = reinterpret_cast<const uint16_t*>(wsb);
-      ba.psi_elem_base = offsets_host[c.first];
-      ba.last_row = reinterpret_cast<const float*>(lrb);
-      ba.offsets = offsets_dev;
-      ba.order = order_dev;
-      ba.seq_begin = c.first;
-      ba.seq_end = c.second;
-      ba.nstates = h->N;
-      ba.path = path_dev;
-      ba.score = score_dev;
-      ba.status = status_dev;
-      ba.obs = obs_dev;
-      ba.rescore_f64 = o.rescore_f64 ? 1 : 0;
-      ba.decode_bt = o.assoc == CV_ASSOC_DECODE ? 1 : 0;
-      ba.pi64 = h->d_pi64.as<double>();
-      ba.a64 = h->d_a64.as<double>();
-      ba.et64 = h->d_et64.as<double>();
-      if (gen_rows) {
-        ba.rows = reinterpret_cast<const float*>(wsb);
-        ba.at = h->d_at32.as<float>();
-        ba.et = h->d_et32.as<float>();
-        ba.assoc = o.assoc;
-        ba.nobs = (int)h->V;
-      }
+      const cvk::GenericBtArgs<float> ba = generic_bt_args(0.0f);
       err = gen_rows ? cvk::launch_generic_bt_rows<float>(ba, n, bts) : cvk::launch_generic_bt<float>(ba, n, bts);
     }
     if (err != hipSuccess) return set_err(CV_EDEVICE, "backtrack launch failed: %s", hipGetErrorString(err));
@@ -1453,14 +1387,10 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
   }
   // the caller's stream sees the whole decode complete
   if (!serial) HIP_TRY(hipStreamWaitEvent(stream, evv[eb + 4 * (chunks.size() - 1) + 3], 0));
-  if (!side_ws && h->acc_on) h->acc_used += nev;
   if (t64_stats_on)  // the counters follow the last backtrack (t64 chunks run on `stream`); nobody waits for them
     HIP_TRY(hipMemcpyAsync(h->t64_stats_pin.p, h->t64_stats.p, (size_t)(cvk::kT64StatSlots + 1) * cvk::kT64StatWords * 8,
                            hipMemcpyDeviceToHost, stream));
-  if (!ws_done) HIP_TRY(hipEventCreateWithFlags(&ws_done, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(ws_done, stream));
-  ws_rec = true;
-  return CV_OK;
+  return end_call(h, side_ws, nev, stream);
 }
 
 // ---- posterior (sum-product) path: cv_posterior_batch* --------------------------------------
@@ -1513,13 +1443,7 @@ cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
     return set_err(CV_EUNSUPPORTED, "the posterior kernels cover N <= %d (N=%d)", cvp::kPostMaxStates, h->N);
   const bool generic = o.kernel == CV_KERNEL_GENERIC || h->N > cvp::kPostMmStates;
   std::vector<int64_t> off_copy;
-  if (!offsets_host) {
-    off_copy.resize((size_t)nseq + 1);
-    HIP_TRY(hipMemcpyAsync(off_copy.data(), offsets_dev, off_copy.size() * 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    offsets_host = off_copy.data();
-  }
-  cv_status st = check_batch(h, nseq, offsets_host);
+  cv_status st = host_offsets(nseq, offsets_host, offsets_dev, off_copy, stream);
   if (st != CV_OK) return st;
   if ((st = ensure_post_tables(h)) != CV_OK) return st;
   const int np = h->pnp;
@@ -1532,60 +1456,26 @@ cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
 
   const bool store = path_dev || gamma_dev;
   const uint64_t per_elem = (uint64_t)np * 8;
-  std::vector<std::pair<int64_t, int64_t>> chunks;
-  uint64_t max_elems = 0;
+  std::vector<cvplan::Chunk> chunks;
   if (!store) {
     chunks.emplace_back(0, nseq);
   } else {
     // 2 KiB of rows per element at N = 256: the f64 trellis's default cap (HBM3E: 288 GB per GPU)
     const uint64_t cap = o.workspace_bytes ? o.workspace_bytes : default_workspace_cap(h->ps_rows.bytes, kDefaultWorkspaceT64);
-    const uint64_t elem_cap = std::max<uint64_t>(cap / per_elem, 1);
-    // equal shares rather than full chunks and a remainder: every launch fills the device alike
-    const uint64_t total_elems = (uint64_t)(offsets_host[nseq] - offsets_host[0]);
-    const uint64_t nchunks = std::max<uint64_t>(1, (total_elems + elem_cap - 1) / elem_cap);
-    const uint64_t target = std::max<uint64_t>(1, (total_elems + nchunks - 1) / nchunks);
-    for (int64_t s0 = 0; s0 < nseq;) {
-      int64_t s1 = s0;
-      uint64_t elems = 0;
-      while (s1 < nseq && s1 - s0 < (1 << 30)) {
-        const uint64_t T = (uint64_t)(offsets_host[s1 + 1] - offsets_host[s1]);
-        if (s1 > s0 && (elems + T > elem_cap || elems + T > target)) break;
-        elems += T;
-        ++s1;
-      }
-      max_elems = std::max(max_elems, elems);
-      chunks.emplace_back(s0, s1);
-      s0 = s1;
-    }
+    const uint64_t max_elems = cvplan::split_equal_shares(offsets_host, nseq, cap / per_elem, chunks).max_elems;
     if ((st = h->ps_rows.ensure((size_t)std::max<uint64_t>(max_elems, 1) * per_elem)) != CV_OK) return st;
   }
   // longest first inside each chunk (stable), so a group's sequences have similar lengths
   const int32_t* order_dev = nullptr;
-  bool varlen = false;
-  const int64_t T0 = offsets_host[1] - offsets_host[0];
-  for (int64_t s = 1; s < nseq && !varlen; ++s) varlen = (offsets_host[s + 1] - offsets_host[s]) != T0;
-  if (varlen) {
+  if (cvplan::varlen(offsets_host, nseq)) {
     if (nseq > INT32_MAX) return set_err(CV_EINVAL, "too many sequences (%lld)", (long long)nseq);
-    std::vector<int32_t>& ord = h->order_host;
-    ord.resize((size_t)nseq);
-    std::iota(ord.begin(), ord.end(), 0);
-    auto len = [&](int32_t x) { return offsets_host[x + 1] - offsets_host[x]; };
-    for (const auto& c : chunks)
-      std::stable_sort(ord.begin() + c.first, ord.begin() + c.second, [&](int32_t x, int32_t y) { return len(x) > len(y); });
-    if ((st = h->ps_order.ensure((size_t)nseq * 4)) != CV_OK) return st;
-    int32_t* pin = h->ps_pin.acquire((size_t)nseq);
-    if (!pin) return set_err(CV_ENOMEM, "pinned staging of %lld order entries failed", (long long)nseq);
-    std::memcpy(pin, ord.data(), (size_t)nseq * 4);
-    HIP_TRY(hipMemcpyAsync(h->ps_order.p, pin, (size_t)nseq * 4, hipMemcpyHostToDevice, stream));
-    HIP_TRY(h->ps_pin.release(stream));
-    order_dev = h->ps_order.as<int32_t>();
+    h->order_host.resize((size_t)nseq);
+    cvplan::longest_first(offsets_host, chunks, h->order_host.data(), nullptr, h->sort_pos);
+    if ((st = upload_order(h->ps_order, h->ps_pin, h->order_host.data(), nseq, stream, &order_dev)) != CV_OK) return st;
   }
   const size_t nev = 4 * chunks.size();
-  if (h->acc_on && h->acc_used + nev > kMaxTimedEvents) h->acc_on = false, h->acc_overflow = true;
-  const size_t eb = h->acc_on ? h->acc_used : 0;
-  h->last_ev_base = eb;
-  for (size_t i = 0; i < nev; ++i)
-    if (!get_event(h->ev, eb + i)) return set_err(CV_EDEVICE, "hipEventCreate failed");
+  size_t eb;
+  if ((st = reserve_events(h, false, nev, &eb)) != CV_OK) return st;
   for (size_t ci = 0; ci < chunks.size(); ++ci) {
     const auto& c = chunks[ci];
     cvp::PostArgs g{};
@@ -1622,11 +1512,7 @@ cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
     HIP_TRY(hipEventRecord(b1, stream));
     h->last_launches = (int64_t)ci + 1;
   }
-  if (h->acc_on) h->acc_used += nev;
-  if (!h->ws_done) HIP_TRY(hipEventCreateWithFlags(&h->ws_done, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(h->ws_done, stream));
-  h->ws_rec = true;
-  return CV_OK;
+  return end_call(h, false, nev, stream);
 }
 
 // ---- K-best (list) Viterbi: cv_kbest_batch* ---------------------------------------------------
@@ -1650,13 +1536,7 @@ cv_status kbest_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, con
     return set_err(CV_EUNSUPPORTED, "the K-best kernels cover N * KT <= %d (N=%d, k=%d: list width KT=%d)",
                    cvkb::kKbestMaxCells, N, k, KT);
   std::vector<int64_t> off_copy;
-  if (!offsets_host) {
-    off_copy.resize((size_t)nseq + 1);
-    HIP_TRY(hipMemcpyAsync(off_copy.data(), offsets_dev, off_copy.size() * 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    offsets_host = off_copy.data();
-  }
-  cv_status st = check_batch(h, nseq, offsets_host);
+  cv_status st = host_offsets(nseq, offsets_host, offsets_dev, off_copy, stream);
   if (st != CV_OK) return st;
   if ((st = ensure_f64_tables(h)) != CV_OK) return st;
   const int S = cvkb::kbest_seqs_per_wg(N, KT, nseq);
@@ -1678,59 +1558,22 @@ cv_status kbest_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, con
                      (long long)s, (unsigned long long)(T * per_elem), (unsigned long long)T, N, KT,
                      (unsigned long long)cap);
   }
-  std::vector<std::pair<int64_t, int64_t>> chunks;
-  uint64_t max_elems = 0;
-  int64_t max_seqs = 0;
-  {
-    // equal shares rather than full chunks and a remainder: every launch fills the device alike
-    const uint64_t total_elems = (uint64_t)(offsets_host[nseq] - offsets_host[0]);
-    const uint64_t nchunks = std::max<uint64_t>(1, (total_elems + elem_cap - 1) / std::max<uint64_t>(elem_cap, 1));
-    const uint64_t target = std::max<uint64_t>(1, (total_elems + nchunks - 1) / nchunks);
-    for (int64_t s0 = 0; s0 < nseq;) {
-      int64_t s1 = s0;
-      uint64_t elems = 0;
-      while (s1 < nseq && s1 - s0 < (1 << 30)) {
-        const uint64_t T = (uint64_t)(offsets_host[s1 + 1] - offsets_host[s1]);
-        if (s1 > s0 && (elems + T > elem_cap || elems + T > target)) break;
-        elems += T;
-        ++s1;
-      }
-      max_elems = std::max(max_elems, elems);
-      max_seqs = std::max(max_seqs, s1 - s0);
-      chunks.emplace_back(s0, s1);
-      s0 = s1;
-    }
-  }
-  if ((st = h->kb_bp.ensure((size_t)std::max<uint64_t>(max_elems, 1) * per_elem)) != CV_OK) return st;
-  if ((st = h->kb_last.ensure((size_t)max_seqs * N * KT * 8)) != CV_OK) return st;
+  std::vector<cvplan::Chunk> chunks;
+  const cvplan::Shares largest = cvplan::split_equal_shares(offsets_host, nseq, elem_cap, chunks);
+  if ((st = h->kb_bp.ensure((size_t)std::max<uint64_t>(largest.max_elems, 1) * per_elem)) != CV_OK) return st;
+  if ((st = h->kb_last.ensure((size_t)largest.max_seqs * N * KT * 8)) != CV_OK) return st;
   if ((st = h->kb_end.ensure((size_t)nseq * k * 4)) != CV_OK) return st;
   // longest first inside each chunk (stable), so a workgroup's sequences have similar lengths
   const int32_t* order_dev = nullptr;
-  bool varlen = false;
-  const int64_t T0 = offsets_host[1] - offsets_host[0];
-  for (int64_t s = 1; s < nseq && !varlen; ++s) varlen = (offsets_host[s + 1] - offsets_host[s]) != T0;
-  if (varlen) {
+  if (cvplan::varlen(offsets_host, nseq)) {
     if (nseq > INT32_MAX) return set_err(CV_EINVAL, "too many sequences (%lld)", (long long)nseq);
-    std::vector<int32_t>& ord = h->order_host;
-    ord.resize((size_t)nseq);
-    std::iota(ord.begin(), ord.end(), 0);
-    auto len = [&](int32_t x) { return offsets_host[x + 1] - offsets_host[x]; };
-    for (const auto& c : chunks)
-      std::stable_sort(ord.begin() + c.first, ord.begin() + c.second, [&](int32_t x, int32_t y) { return len(x) > len(y); });
-    if ((st = h->kb_order.ensure((size_t)nseq * 4)) != CV_OK) return st;
-    int32_t* pin = h->kb_pin.acquire((size_t)nseq);
-    if (!pin) return set_err(CV_ENOMEM, "pinned staging of %lld order entries failed", (long long)nseq);
-    std::memcpy(pin, ord.data(), (size_t)nseq * 4);
-    HIP_TRY(hipMemcpyAsync(h->kb_order.p, pin, (size_t)nseq * 4, hipMemcpyHostToDevice, stream));
-    HIP_TRY(h->kb_pin.release(stream));
-    order_dev = h->kb_order.as<int32_t>();
+    h->order_host.resize((size_t)nseq);
+    cvplan::longest_first(offsets_host, chunks, h->order_host.data(), nullptr, h->sort_pos);
+    if ((st = upload_order(h->kb_order, h->kb_pin, h->order_host.data(), nseq, stream, &order_dev)) != CV_OK) return st;
   }
   const size_t nev = 4 * chunks.size();
-  if (h->acc_on && h->acc_used + nev > kMaxTimedEvents) h->acc_on = false, h->acc_overflow = true;
-  const size_t eb = h->acc_on ? h->acc_used : 0;
-  h->last_ev_base = eb;
-  for (size_t i = 0; i < nev; ++i)
-    if (!get_event(h->ev, eb + i)) return set_err(CV_EDEVICE, "hipEventCreate failed");
+  size_t eb;
+  if ((st = reserve_events(h, false, nev, &eb)) != CV_OK) return st;
   for (size_t ci = 0; ci < chunks.size(); ++ci) {
     const auto& c = chunks[ci];
     cvkb::KbestArgs g{};
@@ -1768,11 +1611,7 @@ cv_status kbest_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, con
     HIP_TRY(hipEventRecord(b1, stream));
     h->last_launches = (int64_t)ci + 1;
   }
-  if (h->acc_on) h->acc_used += nev;
-  if (!h->ws_done) HIP_TRY(hipEventCreateWithFlags(&h->ws_done, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(h->ws_done, stream));
-  h->ws_rec = true;
-  return CV_OK;
+  return end_call(h, false, nev, stream);
 }
 
 cv_opts default_opts() {
@@ -1780,6 +1619,74 @@ cv_opts default_opts() {
   cv_opts_init(&o);
   return o;
 }
+
+// One host-pointer batch call (cv_decode_batch, cv_posterior_batch, cv_kbest_batch,
+// cv_decode_emissions) through the handle's staging buffers; the caller holds h->mu and has
+// selected the device.  stage() checks the caller's arrays and only then enqueues the copies from
+// them; the entry runs its core on the st_* buffers and fetches the results.  obs / path / forced
+// are indexed by absolute element offset: the element slice is [base, total).
+struct HostBatch {
+  cv_hmm* h;
+  int64_t nseq;
+  const int64_t* offsets;
+  const int32_t* obs;  // null: this call stages no observations
+  hipStream_t stream;
+  int64_t base = 0, total = 0;
+  hipError_t err = hipSuccess;  // of the result copies (finish)
+
+  size_t plane() const { return (size_t)std::max<int64_t>(total, 1); }
+
+  // Sizes st_path (`planes` element planes), st_score (`width` per sequence) and st_status too.
+  // check_obs: the host range check (decode only; posterior and K-best report CV_SEQ_BADOBS from
+  // the device).  forced_host: o.forced is the caller's host array -> checked, staged and
+  // rewritten to the device copy (false: it is a validated device array already).
+  cv_status stage(cv_opts& o, size_t planes, size_t width, bool check_obs = false, bool forced_host = true) {
+    cv_status st = check_batch(nseq, offsets);
+    if (st != CV_OK) return st;
+    base = offsets[0], total = offsets[nseq];
+    const int32_t* ob = check_obs ? obs : nullptr;
+    const int32_t* fr = forced_host ? o.forced : nullptr;
+    const int64_t V = h->V, N = h->N;
+    int64_t k;
+    if (ob && (k = first_bad(base, total, [&](int64_t i) { return ob[i] < 0 || ob[i] >= V; })) >= 0)
+      return set_err(CV_EINVAL, "obs[%lld] = %d out of range [0,%lld)", (long long)k, ob[k], (long long)V);
+    if (fr && (k = first_bad(base, total, [&](int64_t i) { return fr[i] < -1 || fr[i] >= N; })) >= 0)
+      return set_err(CV_EINVAL, "forced[%lld] = %d out of range [-1,%d)", (long long)k, fr[k], h->N);
+    if ((st = h->st_off.ensure((size_t)(nseq + 1) * 8)) != CV_OK) return st;
+    if (obs && (st = h->st_obs.ensure(plane() * 4)) != CV_OK) return st;
+    if (planes && (st = h->st_path.ensure(plane() * planes * 4)) != CV_OK) return st;
+    if ((st = h->st_score.ensure((size_t)nseq * width * 8)) != CV_OK) return st;
+    if ((st = h->st_status.ensure((size_t)nseq)) != CV_OK) return st;
+    if (fr && (st = h->st_forced.ensure(plane() * 4)) != CV_OK) return st;
+    HIP_TRY(hipMemcpyAsync(h->st_off.p, offsets, (size_t)(nseq + 1) * 8, hipMemcpyHostToDevice, stream));
+    const size_t n = (size_t)(total - base) * 4;
+    if (obs && n) HIP_TRY(hipMemcpyAsync(h->st_obs.as<int32_t>() + base, obs + base, n, hipMemcpyHostToDevice, stream));
+    if (fr && n) HIP_TRY(hipMemcpyAsync(h->st_forced.as<int32_t>() + base, fr + base, n, hipMemcpyHostToDevice, stream));
+    if (fr) o.forced = h->st_forced.as<int32_t>();
+    return CV_OK;
+  }
+  // a failed core's work is waited for before the caller sees its status
+  cv_status fail(cv_status st) const {
+    (void)hipStreamSynchronize(stream);
+    return st;
+  }
+  // the element slice of plane r of buf (`width` T per element) -> the same slice of out
+  template <typename T>
+  void fetch_elems(T* out, const DevBuf& buf, size_t width = 1, size_t r = 0) {
+    const size_t at = (r * (size_t)total + (size_t)base) * width, n = (size_t)(total - base) * width * sizeof(T);
+    if (err == hipSuccess && n) err = hipMemcpyAsync(out + at, buf.as<T>() + at, n, hipMemcpyDeviceToHost, stream);
+  }
+  // nseq items of `width` T
+  template <typename T>
+  void fetch_seqs(T* out, const DevBuf& buf, size_t width = 1) {
+    if (err == hipSuccess) err = hipMemcpyAsync(out, buf.p, (size_t)nseq * width * sizeof(T), hipMemcpyDeviceToHost, stream);
+  }
+  // the results are in the caller's arrays
+  cv_status finish() {
+    if (err == hipSuccess) err = hipStreamSynchronize(stream);
+    return err == hipSuccess ? CV_OK : set_err(CV_EDEVICE, "copying the results back failed: %s", hipGetErrorString(err));
+  }
+};
 
 }  // namespace
 
@@ -1958,8 +1865,9 @@ CV_API cv_status cv_decode_batch_device(cv_hmm* h, int64_t nseq, const int64_t* 
   if (st != CV_OK) return st;
   const cv_opts o = opts ? *opts : default_opts();
   hipStream_t stream = o.stream ? (hipStream_t)o.stream : h->stream;
-  return decode_device(h, nseq, offsets_host, offsets_dev, obs_dev, o, path_dev, score_dev, status_dev, stream, nullptr,
-                       false, nullptr, nullptr, nullptr, nullptr, nullptr, true);
+  DecodeReq rq;
+  rq.batch_api = true;
+  return decode_device(h, nseq, offsets_host, offsets_dev, obs_dev, o, path_dev, score_dev, status_dev, stream, rq);
 }
 
 // Host-pointer decode; caller holds h->mu and has selected the device.
@@ -1970,50 +1878,17 @@ static cv_status decode_host_locked(cv_hmm* h, int64_t nseq, const int64_t* offs
                                     bool obs_staged = false, bool forced_staged = false, bool batch_api = false) {
   cv_status st;
   if (nseq == 0) return CV_OK;
-  if ((st = check_batch(h, nseq, offsets)) != CV_OK) return st;
-  const int64_t base = offsets[0];
-  const int64_t total = offsets[nseq];  // obs/path are indexed by absolute element offset
-  if (!obs_staged) {
-    const int64_t V = h->V;
-    const int64_t k = first_bad(base, total, [&](int64_t i) { return obs[i] < 0 || obs[i] >= V; });
-    if (k >= 0)
-      return set_err(CV_EINVAL, "obs[%lld] = %d out of range [0,%lld)", (long long)k, obs[k], (long long)h->V);
-  }
-  hipStream_t stream = o.stream ? (hipStream_t)o.stream : h->stream;
-  if ((st = h->st_off.ensure((size_t)(nseq + 1) * 8)) != CV_OK) return st;
-  if ((st = h->st_obs.ensure((size_t)std::max<int64_t>(total, 1) * 4)) != CV_OK) return st;
-  if ((st = h->st_path.ensure((size_t)std::max<int64_t>(total, 1) * 4)) != CV_OK) return st;
-  if ((st = h->st_score.ensure((size_t)nseq * 8)) != CV_OK) return st;
-  if ((st = h->st_status.ensure((size_t)nseq)) != CV_OK) return st;
-  HIP_TRY(hipMemcpyAsync(h->st_off.p, offsets, (size_t)(nseq + 1) * 8, hipMemcpyHostToDevice, stream));
-  if (total > base && !obs_staged)
-    HIP_TRY(hipMemcpyAsync(h->st_obs.as<int32_t>() + base, obs + base, (size_t)(total - base) * 4,
-                           hipMemcpyHostToDevice, stream));
-  if (o.forced && !forced_staged) {  // host forced[] -> device staging, indexed like obs
-    const int32_t N = h->N;
-    const int32_t* fr = o.forced;
-    const int64_t k = first_bad(base, total, [&](int64_t i) { return fr[i] < -1 || fr[i] >= N; });
-    if (k >= 0) return set_err(CV_EINVAL, "forced[%lld] = %d out of range [-1,%d)", (long long)k, o.forced[k], h->N);
-    if ((st = h->st_forced.ensure((size_t)std::max<int64_t>(total, 1) * 4)) != CV_OK) return st;
-    if (total > base)
-      HIP_TRY(hipMemcpyAsync(h->st_forced.as<int32_t>() + base, o.forced + base, (size_t)(total - base) * 4,
-                             hipMemcpyHostToDevice, stream));
-    o.forced = h->st_forced.as<int32_t>();
-  }
+  HostBatch hb{h, nseq, offsets, obs_staged ? nullptr : obs, o.stream ? (hipStream_t)o.stream : h->stream};
+  if ((st = hb.stage(o, 1, 1, true, !forced_staged)) != CV_OK) return st;
+  DecodeReq rq;
+  rq.batch_api = batch_api;
   st = decode_device(h, nseq, offsets, h->st_off.as<int64_t>(), h->st_obs.as<int32_t>(), o, h->st_path.as<int32_t>(),
-                     h->st_score.as<double>(), h->st_status.as<uint8_t>(), stream, nullptr, false, nullptr, nullptr,
-                     nullptr, nullptr, nullptr, batch_api);
-  if (st != CV_OK) {
-    (void)hipStreamSynchronize(stream);
-    return st;
-  }
-  if (total > base)
-    HIP_TRY(hipMemcpyAsync(path_out + base, h->st_path.as<int32_t>() + base, (size_t)(total - base) * 4,
-                           hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(score_out, h->st_score.p, (size_t)nseq * 8, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(status_out, h->st_status.p, (size_t)nseq, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  return CV_OK;
+                     h->st_score.as<double>(), h->st_status.as<uint8_t>(), hb.stream, rq);
+  if (st != CV_OK) return hb.fail(st);
+  hb.fetch_elems(path_out, h->st_path);
+  hb.fetch_seqs(score_out, h->st_score);
+  hb.fetch_seqs(status_out, h->st_status);
+  return hb.finish();
 }
 
 CV_API cv_status cv_decode_batch(cv_hmm* h, int64_t nseq, const int64_t* offsets, const int32_t* obs,
@@ -2056,47 +1931,20 @@ CV_API cv_status cv_posterior_batch(cv_hmm* h, int64_t nseq, const int64_t* offs
   if (st != CV_OK) return st;
   cv_opts o = opts ? *opts : default_opts();
   if (nseq == 0) return CV_OK;
-  if ((st = check_batch(h, nseq, offsets)) != CV_OK) return st;
-  const int64_t base = offsets[0], total = offsets[nseq];
-  const int64_t N = h->N;
-  hipStream_t stream = o.stream ? (hipStream_t)o.stream : h->stream;
-  if ((st = h->st_off.ensure((size_t)(nseq + 1) * 8)) != CV_OK) return st;
-  if ((st = h->st_obs.ensure((size_t)std::max<int64_t>(total, 1) * 4)) != CV_OK) return st;
-  if (path_out && (st = h->st_path.ensure((size_t)std::max<int64_t>(total, 1) * 4)) != CV_OK) return st;
-  if (gamma_out && (st = h->st_gamma.ensure((size_t)std::max<int64_t>(total, 1) * N * 8)) != CV_OK) return st;
-  if ((st = h->st_score.ensure((size_t)nseq * 8)) != CV_OK) return st;
-  if ((st = h->st_status.ensure((size_t)nseq)) != CV_OK) return st;
-  HIP_TRY(hipMemcpyAsync(h->st_off.p, offsets, (size_t)(nseq + 1) * 8, hipMemcpyHostToDevice, stream));
+  const size_t N = (size_t)h->N;
   // the observations are range-checked on the device (CV_SEQ_BADOBS), as in the _device variant
-  if (total > base)
-    HIP_TRY(hipMemcpyAsync(h->st_obs.as<int32_t>() + base, obs + base, (size_t)(total - base) * 4,
-                           hipMemcpyHostToDevice, stream));
-  if (o.forced) {
-    const int32_t* fr = o.forced;
-    const int64_t k = first_bad(base, total, [&](int64_t i) { return fr[i] < -1 || fr[i] >= N; });
-    if (k >= 0) return set_err(CV_EINVAL, "forced[%lld] = %d out of range [-1,%d)", (long long)k, fr[k], h->N);
-    if ((st = h->st_forced.ensure((size_t)std::max<int64_t>(total, 1) * 4)) != CV_OK) return st;
-    if (total > base)
-      HIP_TRY(hipMemcpyAsync(h->st_forced.as<int32_t>() + base, fr + base, (size_t)(total - base) * 4,
-                             hipMemcpyHostToDevice, stream));
-    o.forced = h->st_forced.as<int32_t>();
-  }
+  HostBatch hb{h, nseq, offsets, obs, o.stream ? (hipStream_t)o.stream : h->stream};
+  if ((st = hb.stage(o, path_out ? 1 : 0, 1)) != CV_OK) return st;
+  if (gamma_out && (st = h->st_gamma.ensure(hb.plane() * N * 8)) != CV_OK) return st;
   st = posterior_device(h, nseq, offsets, h->st_off.as<int64_t>(), h->st_obs.as<int32_t>(), o, h->st_score.as<double>(),
                         path_out ? h->st_path.as<int32_t>() : nullptr, gamma_out ? h->st_gamma.as<double>() : nullptr,
-                        h->st_status.as<uint8_t>(), stream);
-  if (st != CV_OK) {
-    (void)hipStreamSynchronize(stream);
-    return st;
-  }
-  if (path_out && total > base)
-    HIP_TRY(hipMemcpyAsync(path_out + base, h->st_path.as<int32_t>() + base, (size_t)(total - base) * 4,
-                           hipMemcpyDeviceToHost, stream));
-  if (gamma_out && total > base)
-    HIP_TRY(hipMemcpyAsync(gamma_out + base * N, h->st_gamma.as<double>() + base * N, (size_t)(total - base) * N * 8,
-                           hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(loglik_out, h->st_score.p, (size_t)nseq * 8, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(status_out, h->st_status.p, (size_t)nseq, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
+                        h->st_status.as<uint8_t>(), hb.stream);
+  if (st != CV_OK) return hb.fail(st);
+  if (path_out) hb.fetch_elems(path_out, h->st_path);
+  if (gamma_out) hb.fetch_elems(gamma_out, h->st_gamma, N);
+  hb.fetch_seqs(loglik_out, h->st_score);
+  hb.fetch_seqs(status_out, h->st_status);
+  if ((st = hb.finish()) != CV_OK) return st;
   for (int64_t s = 0; s < nseq; ++s)
     if (status_out[s] == CV_SEQ_INFEASIBLE)
       return set_err(CV_EINFEASIBLE, "sequence %lld has likelihood 0", (long long)s);
@@ -2133,46 +1981,19 @@ CV_API cv_status cv_kbest_batch(cv_hmm* h, int64_t nseq, const int64_t* offsets,
   if (st != CV_OK) return st;
   cv_opts o = opts ? *opts : default_opts();
   if (nseq == 0) return CV_OK;
-  if ((st = check_batch(h, nseq, offsets)) != CV_OK) return st;
-  const int64_t base = offsets[0], total = offsets[nseq];
-  const int64_t N = h->N;
-  const size_t plane = (size_t)std::max<int64_t>(total, 1);
-  hipStream_t stream = o.stream ? (hipStream_t)o.stream : h->stream;
-  if ((st = h->st_off.ensure((size_t)(nseq + 1) * 8)) != CV_OK) return st;
-  if ((st = h->st_obs.ensure(plane * 4)) != CV_OK) return st;
-  if ((st = h->st_path.ensure(plane * (size_t)k * 4)) != CV_OK) return st;
-  if ((st = h->st_score.ensure((size_t)nseq * k * 8)) != CV_OK) return st;
-  if ((st = h->st_count.ensure((size_t)nseq * 4)) != CV_OK) return st;
-  if ((st = h->st_status.ensure((size_t)nseq)) != CV_OK) return st;
-  HIP_TRY(hipMemcpyAsync(h->st_off.p, offsets, (size_t)(nseq + 1) * 8, hipMemcpyHostToDevice, stream));
   // the observations are range-checked on the device (CV_SEQ_BADOBS), as in the _device variant
-  if (total > base)
-    HIP_TRY(hipMemcpyAsync(h->st_obs.as<int32_t>() + base, obs + base, (size_t)(total - base) * 4,
-                           hipMemcpyHostToDevice, stream));
-  if (o.forced) {
-    const int32_t* fr = o.forced;
-    const int64_t kb = first_bad(base, total, [&](int64_t i) { return fr[i] < -1 || fr[i] >= N; });
-    if (kb >= 0) return set_err(CV_EINVAL, "forced[%lld] = %d out of range [-1,%d)", (long long)kb, fr[kb], h->N);
-    if ((st = h->st_forced.ensure(plane * 4)) != CV_OK) return st;
-    if (total > base)
-      HIP_TRY(hipMemcpyAsync(h->st_forced.as<int32_t>() + base, fr + base, (size_t)(total - base) * 4,
-                             hipMemcpyHostToDevice, stream));
-    o.forced = h->st_forced.as<int32_t>();
-  }
+  HostBatch hb{h, nseq, offsets, obs, o.stream ? (hipStream_t)o.stream : h->stream};
+  if ((st = hb.stage(o, (size_t)k, (size_t)k)) != CV_OK) return st;
+  if ((st = h->st_count.ensure((size_t)nseq * 4)) != CV_OK) return st;
   st = kbest_device(h, nseq, offsets, h->st_off.as<int64_t>(), h->st_obs.as<int32_t>(), k, o, h->st_path.as<int32_t>(),
-                    h->st_score.as<double>(), h->st_count.as<int32_t>(), h->st_status.as<uint8_t>(), stream);
-  if (st != CV_OK) {
-    (void)hipStreamSynchronize(stream);
-    return st;
-  }
-  if (total > base)
-    for (int32_t r = 0; r < k; ++r)  // plane r of the staging and of path_out: offsets[nseq] elements each
-      HIP_TRY(hipMemcpyAsync(path_out + (size_t)r * total + base, h->st_path.as<int32_t>() + (size_t)r * total + base,
-                             (size_t)(total - base) * 4, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(score_out, h->st_score.p, (size_t)nseq * k * 8, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(count_out, h->st_count.p, (size_t)nseq * 4, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(status_out, h->st_status.p, (size_t)nseq, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
+                    h->st_score.as<double>(), h->st_count.as<int32_t>(), h->st_status.as<uint8_t>(), hb.stream);
+  if (st != CV_OK) return hb.fail(st);
+  for (int32_t r = 0; r < k; ++r)  // plane r of the staging and of path_out: offsets[nseq] elements each
+    hb.fetch_elems(path_out, h->st_path, 1, (size_t)r);
+  hb.fetch_seqs(score_out, h->st_score, (size_t)k);
+  hb.fetch_seqs(count_out, h->st_count);
+  hb.fetch_seqs(status_out, h->st_status);
+  if ((st = hb.finish()) != CV_OK) return st;
   for (int64_t s = 0; s < nseq; ++s)
     if (status_out[s] == CV_SEQ_INFEASIBLE)
       return set_err(CV_EINFEASIBLE, "sequence %lld has no path of finite score", (long long)s);
@@ -2204,8 +2025,9 @@ CV_API cv_status cv_decode_emissions_device(cv_hmm* h, int64_t nseq, const int64
   if ((st = set_device(h)) != CV_OK) return st;
   hipStream_t stream = o.stream ? (hipStream_t)o.stream : h->stream;
   const EmisSrc src{emis_dev, ld};
-  return decode_device(h, nseq, offsets_host, offsets_dev, nullptr, o, path_dev, score_dev, status_dev, stream, nullptr,
-                       false, nullptr, nullptr, nullptr, nullptr, &src);
+  DecodeReq rq;
+  rq.emis = &src;
+  return decode_device(h, nseq, offsets_host, offsets_dev, nullptr, o, path_dev, score_dev, status_dev, stream, rq);
 }
 
 CV_API cv_status cv_decode_emissions(cv_hmm* h, int64_t nseq, const int64_t* offsets, const double* emis, int64_t ld,
@@ -2220,49 +2042,28 @@ CV_API cv_status cv_decode_emissions(cv_hmm* h, int64_t nseq, const int64_t* off
   CV_LOCK(h);
   if ((st = set_device(h)) != CV_OK) return st;
   if (nseq == 0) return CV_OK;
-  if ((st = check_batch(h, nseq, offsets)) != CV_OK) return st;
-  const int64_t base = offsets[0], total = offsets[nseq];
   const int64_t N = h->N;
-  const size_t plane = (size_t)std::max<int64_t>(total, 1);
-  hipStream_t stream = o.stream ? (hipStream_t)o.stream : h->stream;
-  if ((st = h->st_off.ensure((size_t)(nseq + 1) * 8)) != CV_OK) return st;
-  if ((st = h->st_emis.ensure((size_t)std::max<int64_t>(total - base, 1) * N * 8)) != CV_OK) return st;
-  if ((st = h->st_path.ensure(plane * 4)) != CV_OK) return st;
-  if ((st = h->st_score.ensure((size_t)nseq * 8)) != CV_OK) return st;
-  if ((st = h->st_status.ensure((size_t)nseq)) != CV_OK) return st;
-  HIP_TRY(hipMemcpyAsync(h->st_off.p, offsets, (size_t)(nseq + 1) * 8, hipMemcpyHostToDevice, stream));
+  HostBatch hb{h, nseq, offsets, nullptr, o.stream ? (hipStream_t)o.stream : h->stream};
+  if ((st = hb.stage(o, 1, 1)) != CV_OK) return st;
+  const int64_t base = hb.base, rows = hb.total - hb.base;
+  if ((st = h->st_emis.ensure((size_t)std::max<int64_t>(rows, 1) * N * 8)) != CV_OK) return st;
   // the N scores of each row, compact on the device (the columns beyond N are never read)
-  if (total > base)
-    HIP_TRY(hipMemcpy2DAsync(h->st_emis.p, (size_t)N * 8, emis + base * ld, (size_t)ld * 8, (size_t)N * 8,
-                             (size_t)(total - base), hipMemcpyHostToDevice, stream));
-  if (o.forced) {  // host forced[] -> device staging, indexed like the elements
-    const int32_t* fr = o.forced;
-    const int64_t k = first_bad(base, total, [&](int64_t i) { return fr[i] < -1 || fr[i] >= N; });
-    if (k >= 0) return set_err(CV_EINVAL, "forced[%lld] = %d out of range [-1,%d)", (long long)k, fr[k], h->N);
-    if ((st = h->st_forced.ensure(plane * 4)) != CV_OK) return st;
-    if (total > base)
-      HIP_TRY(hipMemcpyAsync(h->st_forced.as<int32_t>() + base, fr + base, (size_t)(total - base) * 4,
-                             hipMemcpyHostToDevice, stream));
-    o.forced = h->st_forced.as<int32_t>();
-  }
+  if (rows > 0)
+    HIP_TRY(hipMemcpy2DAsync(h->st_emis.p, (size_t)N * 8, emis + base * ld, (size_t)ld * 8, (size_t)N * 8, (size_t)rows,
+                             hipMemcpyHostToDevice, hb.stream));
   // row e of the staging at p + e * N: the staging holds the elements from `base` on
   const EmisSrc src{reinterpret_cast<const double*>(reinterpret_cast<uintptr_t>(h->st_emis.p) -
                                                     (uintptr_t)base * (uintptr_t)N * 8),
                     N};
+  DecodeReq rq;
+  rq.emis = &src;
   st = decode_device(h, nseq, offsets, h->st_off.as<int64_t>(), nullptr, o, h->st_path.as<int32_t>(),
-                     h->st_score.as<double>(), h->st_status.as<uint8_t>(), stream, nullptr, false, nullptr, nullptr,
-                     nullptr, nullptr, &src);
-  if (st != CV_OK) {
-    (void)hipStreamSynchronize(stream);
-    return st;
-  }
-  if (total > base)
-    HIP_TRY(hipMemcpyAsync(path_out + base, h->st_path.as<int32_t>() + base, (size_t)(total - base) * 4,
-                           hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(score_out, h->st_score.p, (size_t)nseq * 8, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(status_out, h->st_status.p, (size_t)nseq, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  return CV_OK;
+                     h->st_score.as<double>(), h->st_status.as<uint8_t>(), hb.stream, rq);
+  if (st != CV_OK) return hb.fail(st);
+  hb.fetch_elems(path_out, h->st_path);
+  hb.fetch_seqs(score_out, h->st_score);
+  hb.fetch_seqs(status_out, h->st_status);
+  return hb.finish();
 }
 
 // ---- consistency-constrained decode --------------------------------------------------------
@@ -2364,7 +2165,7 @@ cv_status constrained_validate(cv_hmm* h, int64_t nseq, const int64_t* offsets, 
   cs.clear();
   if (nseq == 0) return CV_OK;
   cv_status st;
-  if ((st = check_batch(h, nseq, offsets)) != CV_OK) return st;
+  if ((st = check_batch(nseq, offsets)) != CV_OK) return st;
   {
     const int64_t V = h->V;
     int64_t k = first_bad(offsets[0], offsets[nseq], [&](int64_t i) { return obs[i] < 0 || obs[i] >= V; });
@@ -3051,8 +2852,10 @@ cv_status side_decode_launch(cv_hmm* h, int64_t nseq, const int64_t* offsets_hos
   cv_opts o2 = o;
   o2.forced = nullptr;
   o2.rescore_f64 = 0;  // f64: the decode's score is the reference's
+  DecodeReq side_rq;
+  side_rq.side_ws = true;
   if ((st = decode_device(h, nu, off2, off2_d, sd.obs2.as<int32_t>(), o2, sd.path2.as<int32_t>(), score2, status2,
-                          sd.stream, nullptr, /*side_ws=*/true)) != CV_OK) {
+                          sd.stream, side_rq)) != CV_OK) {
     if (st != CV_ENOMEM) return st;
     // the side workspace did not fit beside the terms pass's buffers: drop the side decode (its
     // staging kernel wrote only side buffers) and let the final forced decode cover these
@@ -3249,8 +3052,10 @@ cv_status forced_decode_resume(cv_hmm* h, int64_t nseq, const int64_t* offsets_h
   cv_opts o2 = o;
   o2.forced = h->rs_frc2.as<int32_t>();
   o2.rescore_f64 = 0;  // f32: re-scored below over the whole sequences; f64: the score is exact
+  DecodeReq resume_rq;
+  resume_rq.resume_rows = h->rs_resume.p;
   if ((st = decode_device(h, nm, off2, off2_d, h->rs_obs2.as<int32_t>(), o2, h->rs_path2.as<int32_t>(), score2,
-                          status2, stream, h->rs_resume.p)) != CV_OK) {
+                          status2, stream, resume_rq)) != CV_OK) {
     (void)hipStreamSynchronize(stream);
     (void)hipStreamSynchronize(h->bt_stream);
     return st;
@@ -3452,7 +3257,7 @@ CV_API cv_status cv_decode_forced_components(cv_hmm* h, int64_t nseq, const int6
   if (o.forced) return set_err(CV_EINVAL, "opts->forced is derived from component/comp_state");
   if (objective_out) *objective_out = 0.0;
   if (nseq == 0) return CV_OK;
-  if ((st = check_batch(h, nseq, offsets)) != CV_OK) return st;
+  if ((st = check_batch(nseq, offsets)) != CV_OK) return st;
   {
     const int64_t k =
         first_bad(offsets[0], offsets[nseq], [&](int64_t i) { return component[i] < -1 || component[i] >= ncomp; });
@@ -3486,7 +3291,7 @@ CV_API cv_status cv_decode_constrained_device(cv_hmm* h, int64_t nseq, const int
   if (constrained_dtype_check(h, o) != CV_OK) return CV_EUNSUPPORTED;
   if (o.forced) return set_err(CV_EINVAL, "opts->forced is set by the constrained decode itself");
   if (nseq == 0) return CV_OK;
-  if ((st = check_batch(h, nseq, offsets_host)) != CV_OK) return st;
+  if ((st = check_batch(nseq, offsets_host)) != CV_OK) return st;
   hipStream_t stream = o.stream ? (hipStream_t)o.stream : h->stream;
   // the handle's shared buffers (ws_order, cs_zero, st_status) may still be in use by a
   // cv_decode_batch_device call on another stream: wait for it on this one
@@ -3972,9 +3777,11 @@ cv_status superseq_cp_par(cv_hmm* h, int64_t nseq, const int64_t* offsets, const
       trace_mark("chain: obs H2D (first part)");
     }
     const size_t c0 = dchunks.size();
+    DecodeReq part_rq;
+    part_rq.cp_cert = d_cert.as<double>() + 2 * s0;
+    part_rq.chunks_out = &dchunks;
     st = decode_device(h, s1 - s0, off.data() + s0, d_off.as<int64_t>() + s0, d_obs.as<int32_t>(), o,
-                       d_path.as<int32_t>(), d_score + s0, d_status + s0, stream, nullptr, false,
-                       d_cert.as<double>() + 2 * s0, nullptr, nullptr, &dchunks);
+                       d_path.as<int32_t>(), d_score + s0, d_status + s0, stream, part_rq);
     if (st == CV_EUNSUPPORTED && !small) {  // no rows to certify (generic_rows = 0): the serial chain
       g_err.clear();                         // runs, and the public call succeeds
       return CV_OK;
@@ -4580,9 +4387,12 @@ cv_status superseq_cp_par(cv_hmm* h, int64_t nseq, const int64_t* offsets, const
     cvk::TuningOverride prio(&cvk::Tuning::generic_prio,
                              beside_fwd && h->tuning.chain_spec_prio ? 1 : h->tuning.generic_prio);
     // the side workspace: the main one may still hold the last part's forward pass
+    DecodeReq spec_rq;
+    spec_rq.side_ws = true;
+    spec_rq.cp_init = d_sinit.as<double>();
+    spec_rq.cp_last = d_slast.as<double>();
     if ((st = decode_device(h, nf, so.data(), d_soff.as<int64_t>(), d_sobs.as<int32_t>(), oc, d_spath.as<int32_t>(), sc,
-                            reinterpret_cast<uint8_t*>(sc + nf), cs, nullptr, true, nullptr, d_sinit.as<double>(),
-                            d_slast.as<double>())) != CV_OK)
+                            reinterpret_cast<uint8_t*>(sc + nf), cs, spec_rq)) != CV_OK)
       return st;
     }
     spec_path.resize((size_t)Ls);
@@ -4717,7 +4527,7 @@ CV_API cv_status cv_decode_superseq_cp(cv_hmm* h, int64_t nseq, const int64_t* o
   CV_LOCK(h);
   cv_status st = set_device(h);
   if (st != CV_OK) return st;
-  if ((st = check_batch(h, nseq, offsets)) != CV_OK) return st;
+  if ((st = check_batch(nseq, offsets)) != CV_OK) return st;
   const int64_t base = offsets[0], L = offsets[nseq] - base;
   if (L <= 0) return CV_OK;
   auto check_obs = [&]() -> cv_status {
@@ -4832,7 +4642,7 @@ CV_API cv_status cv_solver_create(const char* kind, cv_hmm* h, const cv_superseq
   s->nseq = d->nseq;
   s->offsets.assign(d->offsets, d->offsets + d->nseq + 1);
   if (s->offsets.empty()) s->offsets.push_back(0);
-  cv_status st = check_batch(h, s->nseq, s->offsets.data());
+  cv_status st = check_batch(s->nseq, s->offsets.data());
   if (st != CV_OK) return st;
   if (s->offsets[0] != 0) return set_err(CV_EINVAL, "super-sequence offsets must start at 0");
   const int64_t total = s->offsets.back();

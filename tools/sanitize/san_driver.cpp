@@ -3,18 +3,23 @@
 //   hmm_json.cpp  the hmm.json reader/writer (malformed files, nulls, round trips)
 //   csp.cpp       exact term accumulation (add_exact), pair lists, the component search
 //   hostscan.cpp  the constrained decode's component scan vs a scalar loop (both builds)
+//   batchplan.cpp the batch planner (chunk splits, longest-first order) vs plain loops, hand-
+//                 worked splits, offsets and caps at the edge of 64 bits
 //   exact_fixed.h nearbyint(x * 2^64) limbs for f32 and f64 vs an __int128 reference
 // Built with g++ -fsanitize=address,undefined (tools/sanitize/Makefile); runs in the
 // container, never on the GPU box.  Exit status 0 = every check passed with no sanitizer
 // report (UBSan is built with -fno-sanitize-recover, so any report aborts).
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <numeric>
 #include <random>
 #include <string>
 #include <vector>
 
+#include "../../consistent-viterbi_amd/csrc/batchplan.hpp"
 #include "../../consistent-viterbi_amd/csrc/csp.hpp"
 #include "../../consistent-viterbi_amd/csrc/exact_fixed.h"
 #include "../../consistent-viterbi_amd/csrc/hmm_json.hpp"
@@ -209,6 +214,193 @@ static void check_hostscan() {
   }
 }
 
+// ---- batchplan.cpp --------------------------------------------------------------------------
+using Chunks = std::vector<cvplan::Chunk>;
+
+static std::vector<int64_t> offsets_of(const std::vector<int64_t>& lengths, int64_t base = 0) {
+  std::vector<int64_t> off(lengths.size() + 1, base);
+  for (size_t s = 0; s < lengths.size(); ++s) off[s + 1] = off[s] + lengths[s];
+  return off;
+}
+
+// contiguous, non-empty, covering [0, nseq); over elem_cap elements only as a single sequence
+static void check_chunks(const Chunks& ch, const std::vector<int64_t>& off, uint64_t elem_cap) {
+  const int64_t nseq = (int64_t)off.size() - 1;
+  CHECK(!ch.empty() && ch.front().first == 0 && ch.back().second == nseq);
+  for (size_t i = 0; i < ch.size(); ++i) {
+    CHECK(ch[i].first < ch[i].second);
+    if (i) CHECK(ch[i].first == ch[i - 1].second);
+    const uint64_t elems = (uint64_t)(off[(size_t)ch[i].second] - off[(size_t)ch[i].first]);
+    CHECK(elems <= elem_cap || ch[i].second - ch[i].first == 1);
+  }
+}
+
+// the order of every chunk against std::stable_sort of the identity and, with pairing, against
+// a greedy scan of that sorted list (pairs of equal-length neighbours first, leftovers after)
+static void check_order(const Chunks& ch, const std::vector<int64_t>& off, std::vector<int64_t>& scratch) {
+  const size_t nseq = off.size() - 1;
+  auto len = [&](int32_t x) { return off[(size_t)x + 1] - off[(size_t)x]; };
+  std::vector<int32_t> plain(nseq, -1), paired(nseq, -1);
+  std::vector<int64_t> npair(ch.size(), -1);
+  cvplan::longest_first(off.data(), ch, plain.data(), nullptr, scratch);
+  cvplan::longest_first(off.data(), ch, paired.data(), npair.data(), scratch);
+  for (size_t ci = 0; ci < ch.size(); ++ci) {
+    const size_t b = (size_t)ch[ci].first, e = (size_t)ch[ci].second;
+    std::vector<int32_t> ref(e - b);
+    std::iota(ref.begin(), ref.end(), (int32_t)b);
+    std::stable_sort(ref.begin(), ref.end(), [&](int32_t x, int32_t y) { return len(x) > len(y); });
+    CHECK(std::equal(ref.begin(), ref.end(), plain.begin() + (long)b));
+    std::vector<int32_t> pairs, tail;
+    for (size_t i = 0; i < ref.size();) {
+      if (i + 1 < ref.size() && len(ref[i]) == len(ref[i + 1])) {
+        pairs.push_back(ref[i]), pairs.push_back(ref[i + 1]);
+        i += 2;
+      } else {
+        tail.push_back(ref[i++]);
+      }
+    }
+    CHECK(npair[ci] == (int64_t)pairs.size() / 2);
+    if (npair[ci] != (int64_t)pairs.size() / 2) continue;
+    for (size_t i = 0; i + 1 < pairs.size(); i += 2) CHECK(len(paired[b + i]) == len(paired[b + i + 1]));
+    for (size_t i = b + pairs.size(); i + 1 < e; ++i)  // the tail: longest first, ties by index
+      CHECK(len(paired[i]) > len(paired[i + 1]) || (len(paired[i]) == len(paired[i + 1]) && paired[i] < paired[i + 1]));
+    CHECK(std::equal(pairs.begin(), pairs.end(), paired.begin() + (long)b));
+    CHECK(std::equal(tail.begin(), tail.end(), paired.begin() + (long)(b + pairs.size())));
+  }
+}
+
+// the decode's split as plain loops: equal shares of the batch under half the cap (the whole cap
+// when serial), then, for equal lengths, whole rounds of `unit` sequences per chunk
+static Chunks ref_pipelined(const std::vector<int64_t>& off, const cvplan::Pipeline& p) {
+  const int64_t nseq = (int64_t)off.size() - 1;
+  const uint64_t total = (uint64_t)(off.back() - off.front());
+  const uint64_t half_cap = std::max<uint64_t>(p.serial ? p.cap : p.cap / 2, p.per_elem_all);
+  uint64_t nchunks = std::max<uint64_t>(1, (total * p.per_elem_all + half_cap - 1) / half_cap);
+  if (!p.serial) nchunks = std::max<uint64_t>(nchunks, std::min<uint64_t>(p.max_chunks, (uint64_t)(nseq / 2048)));
+  const uint64_t target = std::max<uint64_t>(1, (total + nchunks - 1) / nchunks);
+  const uint64_t elem_cap = std::max<uint64_t>(half_cap / p.per_elem_all, 1);
+  Chunks ch;
+  uint64_t elems = 0;
+  int64_t s0 = 0;
+  for (int64_t s = 0; s < nseq; ++s) {
+    const uint64_t T = (uint64_t)(off[(size_t)s + 1] - off[(size_t)s]);
+    if (s > s0 && (elems + T > elem_cap || elems + T > target)) ch.emplace_back(s0, s), s0 = s, elems = 0;
+    elems += T;
+  }
+  ch.emplace_back(s0, nseq);
+  const int64_t T0 = off[1] - off[0];
+  bool uniform = T0 > 0;
+  for (int64_t s = 1; s < nseq; ++s) uniform &= off[(size_t)s + 1] - off[(size_t)s] == T0;
+  if (!uniform || ch.size() == 1) return ch;
+  const int64_t cap_seqs = (int64_t)std::min<uint64_t>(std::max<uint64_t>(elem_cap / (uint64_t)T0, 1), INT64_MAX / 2);
+  int64_t per = (nseq + (int64_t)ch.size() - 1) / (int64_t)ch.size();
+  while (per % p.unit) ++per;
+  if (per > cap_seqs) per = cap_seqs >= p.unit ? cap_seqs - cap_seqs % p.unit : cap_seqs;
+  ch.clear();
+  for (s0 = 0; s0 < nseq; s0 += per) ch.emplace_back(s0, std::min(nseq, s0 + per));
+  return ch;
+}
+
+static void check_batchplan() {
+  char msg[64];
+  const int64_t good[3] = {2, 2, 5}, down[3] = {0, 4, 3}, neg[2] = {-1, 3}, longer[2] = {0, (int64_t)INT32_MAX + 1};
+  CHECK(cvplan::check_offsets(2, good, msg) && cvplan::check_offsets(0, good, msg));
+  CHECK(!cvplan::check_offsets(-1, good, msg) && !std::strcmp(msg, "nseq < 0"));
+  CHECK(!cvplan::check_offsets(1, nullptr, msg) && !std::strcmp(msg, "offsets is NULL"));
+  CHECK(!cvplan::check_offsets(1, neg, msg) && !std::strcmp(msg, "offsets[0] < 0"));
+  CHECK(!cvplan::check_offsets(2, down, msg) && !std::strcmp(msg, "offsets not non-decreasing at 1"));
+  CHECK(!cvplan::check_offsets(1, longer, msg) && !std::strcmp(msg, "sequence 0 too long"));
+
+  // hand-worked splits
+  Chunks ch;
+  std::vector<int64_t> scratch;
+  const std::vector<int64_t> five = offsets_of({5, 3, 4, 2, 6});
+  const cvplan::Shares sh = cvplan::split_equal_shares(five.data(), 5, 8, ch);
+  CHECK((ch == Chunks{{0, 1}, {1, 3}, {3, 4}, {4, 5}}) && sh.max_elems == 7 && sh.max_seqs == 2);
+  for (int64_t unit : {1, 2, 64, 16384}) {
+    cvplan::split_pipelined(five.data(), 5, {4, 64, true, 8, unit}, ch);
+    CHECK((ch == Chunks{{0, 2}, {2, 4}, {4, 5}}));
+    cvplan::split_pipelined(five.data(), 5, {4, 64, false, 8, unit}, ch);
+    CHECK((ch == Chunks{{0, 1}, {1, 3}, {3, 4}, {4, 5}}));
+  }
+  const std::vector<int64_t> ten = offsets_of(std::vector<int64_t>(10, 4));
+  cvplan::split_pipelined(ten.data(), 10, {4, 64, true, 8, 3}, ch);
+  CHECK((ch == Chunks{{0, 3}, {3, 6}, {6, 9}, {9, 10}}));
+  cvplan::split_pipelined(ten.data(), 10, {4, 64, true, 8, 4}, ch);
+  CHECK((ch == Chunks{{0, 4}, {4, 8}, {8, 10}}));
+
+  // properties over seeded random batches
+  std::mt19937_64 rng(13);
+  for (int trial = 0; trial < 4000; ++trial) {
+    const int64_t nseq = 1 + (int64_t)(rng() % 300);
+    const int mode = (int)(rng() % 6);  // 0: all zero, 1: all equal, 2: few distinct lengths, else ragged
+    const int64_t same = 1 + (int64_t)(rng() % 70);
+    std::vector<int64_t> lengths((size_t)nseq);
+    for (int64_t& T : lengths) T = mode == 0 ? 0 : mode == 1 ? same : mode == 2 ? 3 * (int64_t)(rng() % 4) : (int64_t)(rng() % 71);
+    const std::vector<int64_t> off = offsets_of(lengths, (int64_t)(rng() % 1000));
+    const uint64_t total = (uint64_t)(off.back() - off.front());
+    CHECK(cvplan::check_offsets(nseq, off.data(), msg));
+    bool ragged = false;
+    for (int64_t T : lengths) ragged |= T != lengths[0];
+    CHECK(cvplan::varlen(off.data(), nseq) == ragged);
+
+    const uint64_t elem_cap = rng() % 4 == 0 ? rng() % 3 : rng() % (total + 10);
+    const cvplan::Shares got = cvplan::split_equal_shares(off.data(), nseq, elem_cap, ch);
+    check_chunks(ch, off, std::max<uint64_t>(elem_cap, 1));
+    uint64_t max_elems = 0;
+    int64_t max_seqs = 0;
+    for (const auto& c : ch) {
+      uint64_t elems = 0;
+      for (int64_t s = c.first; s < c.second; ++s) elems += (uint64_t)lengths[(size_t)s];
+      max_elems = std::max(max_elems, elems);
+      max_seqs = std::max(max_seqs, c.second - c.first);
+    }
+    CHECK(got.max_elems == max_elems && got.max_seqs == max_seqs);
+    if (elem_cap >= std::max<uint64_t>(total, 1)) CHECK(ch.size() == 1);
+    check_order(ch, off, scratch);
+
+    cvplan::Pipeline p;
+    p.per_elem_all = 1 + rng() % 64;
+    p.cap = rng() % 4 == 0 ? rng() % (2 * p.per_elem_all) : rng() % (2 * (total + 10) * p.per_elem_all);
+    p.serial = rng() % 2;
+    p.max_chunks = 1 + rng() % 8;
+    p.unit = 1 + (int64_t)(rng() % 130);
+    cvplan::split_pipelined(off.data(), nseq, p, ch);
+    CHECK(ch == ref_pipelined(off, p));
+    const uint64_t half_cap = std::max<uint64_t>(p.serial ? p.cap : p.cap / 2, p.per_elem_all);
+    check_chunks(ch, off, half_cap / p.per_elem_all);
+    if (half_cap / p.per_elem_all >= std::max<uint64_t>(total, 1)) CHECK(ch.size() == 1);
+    const cvplan::Shares m = cvplan::measure(off.data(), ch);
+    CHECK(m.max_elems <= std::max<uint64_t>(half_cap / p.per_elem_all, 70) && m.max_seqs >= 1);
+    check_order(ch, off, scratch);
+  }
+
+  // both sides of the counting-sort threshold (longest <= 4 n + 65,536): n = 6
+  for (int64_t longest : {(int64_t)65560, (int64_t)65561, (int64_t)70000}) {
+    const std::vector<int64_t> off = offsets_of({7, longest, 7, 0, longest, 9});
+    check_order(Chunks{{0, 6}}, off, scratch);
+    check_order(Chunks{{0, 2}, {2, 6}}, off, scratch);
+  }
+
+  // offsets near INT64_MAX / per_elem and a cap of UINT64_MAX: no signed overflow
+  for (uint64_t per_elem : {(uint64_t)1, (uint64_t)2, (uint64_t)2048, (uint64_t)1 << 20}) {
+    const int64_t top = (int64_t)((uint64_t)INT64_MAX / per_elem);
+    for (const std::vector<int64_t>& off :
+         {std::vector<int64_t>{top - 40, top - 30, top - 30, top - 5, top}, std::vector<int64_t>{0, top / 2, top},
+          std::vector<int64_t>{0, top / 4, top / 2, 3 * (top / 4), top}}) {
+      const int64_t nseq = (int64_t)off.size() - 1;
+      for (uint64_t cap : {UINT64_MAX, UINT64_MAX / 2, per_elem, (uint64_t)0})
+        for (bool serial : {false, true}) {
+          cvplan::split_pipelined(off.data(), nseq, {per_elem, cap, serial, 8, 64 * 256}, ch);
+          check_chunks(ch, off, std::max<uint64_t>(std::max<uint64_t>(serial ? cap : cap / 2, per_elem) / per_elem, 1));
+          check_order(ch, off, scratch);
+          cvplan::split_equal_shares(off.data(), nseq, cap / per_elem, ch);
+          check_chunks(ch, off, std::max<uint64_t>(cap / per_elem, 1));
+        }
+    }
+  }
+}
+
 static void check_json() {
   const std::string good =
       "{\"a\":{\"v\":1,\"dim\":[2,2],\"data\":[-0.1549019599857432,-0.5228787452803376,null,0.0]},"
@@ -250,6 +442,7 @@ static void check_json() {
 
 int main() {
   check_hostscan();
+  check_batchplan();
   check_exact_fixed();
   check_add_exact();
   check_csp();
