@@ -270,6 +270,7 @@ struct cv_hmm {
   // posterior workspace: the scaled forward rows of one chunk, the longest-first order, and the
   // host API's gamma staging
   DevBuf ps_rows, ps_order, st_gamma;
+  DevBuf ps_kshift;  // cv_posterior_emissions*: each sequence's sum of row-scale exponents (int64)
   OrderStage ps_pin;
   // K-best workspace: the u16 back-pointers of one chunk, each sequence's last lists, the
   // longest-first order, the ranks' end points, and the host API's count staging
@@ -1427,12 +1428,8 @@ cv_status ensure_post_tables(cv_hmm* h) {
   return CV_OK;
 }
 
-// Core of cv_posterior_batch*: all pointers are device pointers except offsets_host.  Chunks of
-// whole sequences (original order) whose forward rows fit the workspace cap run forward then
-// backward on `stream`; scoring mode (no path, no gamma) is one forward launch with no rows.
-cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, const int64_t* offsets_dev,
-                           const int32_t* obs_dev, const cv_opts& o, double* loglik_dev, int32_t* path_dev,
-                           double* gamma_dev, uint8_t* status_dev, hipStream_t stream) {
+// What the posterior path accepts of the options and the model (no device needed).
+cv_status posterior_opts_ok(const cv_hmm* h, const cv_opts& o) {
   if (o.dtype == CV_DTYPE_F32) return set_err(CV_EUNSUPPORTED, "the posterior path is f64 only");
   if (o.dtype != CV_DTYPE_F64) return set_err(CV_EINVAL, "bad dtype %d", o.dtype);
   if (o.assoc != CV_ASSOC_VITERBI)
@@ -1441,10 +1438,25 @@ cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
     return set_err(CV_EINVAL, "posterior kernel must be AUTO or GENERIC (kernel %d)", o.kernel);
   if (h->N > cvp::kPostMaxStates)
     return set_err(CV_EUNSUPPORTED, "the posterior kernels cover N <= %d (N=%d)", cvp::kPostMaxStates, h->N);
+  return CV_OK;
+}
+
+// Core of cv_posterior_batch*: all pointers are device pointers except offsets_host.  Chunks of
+// whole sequences (original order) whose forward rows fit the workspace cap run forward then
+// backward on `stream`; scoring mode (no path, no gamma) is one forward launch with no rows.
+// emis (cv_posterior_emissions*): the emissions of every element come from this dense array
+// of log10 scores instead of the handle's b through obs_dev (ignored, may be null).  Each chunk's
+// rows are staged in probability space behind its forward rows (emis_prepare_lin_f64: 8 NP + 4
+// bytes per element more, under the same cap -- so the scoring mode is chunked too) and stay
+// there until its backward pass has run; the sequences' row-scale exponents go to ps_kshift.
+cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, const int64_t* offsets_dev,
+                           const int32_t* obs_dev, const cv_opts& o, double* loglik_dev, int32_t* path_dev,
+                           double* gamma_dev, uint8_t* status_dev, hipStream_t stream, const EmisSrc* emis = nullptr) {
+  cv_status st = posterior_opts_ok(h, o);
+  if (st != CV_OK) return st;
   const bool generic = o.kernel == CV_KERNEL_GENERIC || h->N > cvp::kPostMmStates;
   std::vector<int64_t> off_copy;
-  cv_status st = host_offsets(nseq, offsets_host, offsets_dev, off_copy, stream);
-  if (st != CV_OK) return st;
+  if ((st = host_offsets(nseq, offsets_host, offsets_dev, off_copy, stream)) != CV_OK) return st;
   if ((st = ensure_post_tables(h)) != CV_OK) return st;
   const int np = h->pnp;
   h->last_launches = 0;
@@ -1455,15 +1467,37 @@ cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
   if (h->ws_rec) HIP_TRY(hipStreamWaitEvent(stream, h->ws_done, 0));
 
   const bool store = path_dev || gamma_dev;
-  const uint64_t per_elem = (uint64_t)np * 8;
+  const uint64_t row_bytes = (uint64_t)np * 8;
+  const uint64_t per_elem = (store ? row_bytes : 0) + (emis ? row_bytes + 4 : 0);
   std::vector<cvplan::Chunk> chunks;
-  if (!store) {
+  uint64_t max_elems = 0;
+  if (per_elem == 0) {
     chunks.emplace_back(0, nseq);
   } else {
     // 2 KiB of rows per element at N = 256: the f64 trellis's default cap (HBM3E: 288 GB per GPU)
     const uint64_t cap = o.workspace_bytes ? o.workspace_bytes : default_workspace_cap(h->ps_rows.bytes, kDefaultWorkspaceT64);
-    const uint64_t max_elems = cvplan::split_equal_shares(offsets_host, nseq, cap / per_elem, chunks).max_elems;
-    if ((st = h->ps_rows.ensure((size_t)std::max<uint64_t>(max_elems, 1) * per_elem)) != CV_OK) return st;
+    uint64_t elem_cap = cap / per_elem;
+    if (emis) {  // the staged rows of a sequence cannot be split, and a chunk is indexed by int32
+      elem_cap = std::min<uint64_t>(elem_cap, INT32_MAX);
+      for (int64_t s = 0; s < nseq; ++s) {
+        const uint64_t T = (uint64_t)(offsets_host[s + 1] - offsets_host[s]);
+        if (T > INT32_MAX) return set_err(CV_ELIMIT, "sequence %lld: %llu elements of dense emissions", (long long)s, (unsigned long long)T);
+        if (T > elem_cap)
+          return set_err(CV_ENOMEM, "sequence %lld needs %llu bytes of staged emissions and rows (T=%llu, NP=%d), workspace cap %llu",
+                         (long long)s, (unsigned long long)(T * per_elem), (unsigned long long)T, np, (unsigned long long)cap);
+      }
+    }
+    max_elems = std::max<uint64_t>(cvplan::split_equal_shares(offsets_host, nseq, elem_cap, chunks).max_elems, 1);
+    if ((st = h->ps_rows.ensure((size_t)(max_elems * per_elem))) != CV_OK) return st;
+  }
+  // the workspace: [max_elems][NP] forward rows (store), [max_elems][NP] staged emission rows,
+  // [max_elems] int32 observation indices (emis); NP * 8 is a multiple of 512
+  double* const ws_rows = store ? h->ps_rows.as<double>() : nullptr;
+  double* const ws_emis = emis ? h->ps_rows.as<double>() + (store ? max_elems * (uint64_t)np : 0) : nullptr;
+  int32_t* const ws_idx = emis ? reinterpret_cast<int32_t*>(ws_emis + max_elems * (uint64_t)np) : nullptr;
+  if (emis) {
+    if ((st = h->ps_kshift.ensure((size_t)nseq * 8)) != CV_OK) return st;
+    HIP_TRY(hipMemsetAsync(h->ps_kshift.p, 0, (size_t)nseq * 8, stream));
   }
   // longest first inside each chunk (stable), so a group's sequences have similar lengths
   const int32_t* order_dev = nullptr;
@@ -1493,7 +1527,7 @@ cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
     g.nstates = h->N;
     g.np = np;
     g.nobs = h->V;
-    g.rows = store ? h->ps_rows.as<double>() : nullptr;
+    g.rows = ws_rows;
     g.loglik = loglik_dev;
     g.status = status_dev;
     g.path = path_dev;
@@ -1501,7 +1535,31 @@ cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
     g.dump = h->p_dump.as<double>();
     hipEvent_t f0 = h->ev[eb + 4 * ci], f1 = h->ev[eb + 4 * ci + 1], b0 = h->ev[eb + 4 * ci + 2], b1 = h->ev[eb + 4 * ci + 3];
     HIP_TRY(hipEventRecord(f0, stream));
-    hipError_t err = cvp::launch_post_fwd(g, generic, stream);
+    hipError_t err;
+    if (emis) {
+      const int64_t e0 = offsets_host[c.first], e1 = offsets_host[c.second];
+      cvem::EmisLinArgs eg{};
+      eg.src = emis->p;
+      eg.ld = emis->ld;
+      eg.e0 = e0;
+      eg.nrows = e1 - e0;
+      eg.nstates = h->N;
+      eg.stride = np;
+      eg.dst = ws_emis;
+      eg.idx = ws_idx;
+      eg.offsets = offsets_dev;
+      eg.seq_begin = c.first;
+      eg.seq_end = c.second;
+      eg.kshift = h->ps_kshift.as<int64_t>();
+      err = cvem::launch_emis_prepare_lin(eg, h->cus, stream);
+      if (err != hipSuccess) return set_err(CV_EDEVICE, "emission staging launch failed: %s", hipGetErrorString(err));
+      g.et = ws_emis;
+      // the kernels index obs by absolute element: (idx - e0)[e] = idx[e - e0]
+      g.obs = reinterpret_cast<const int32_t*>(reinterpret_cast<uintptr_t>(ws_idx) - (uintptr_t)e0 * 4);
+      g.nobs = e1 - e0;
+      g.kshift = h->ps_kshift.as<int64_t>();
+    }
+    err = cvp::launch_post_fwd(g, generic, stream);
     if (err != hipSuccess) return set_err(CV_EDEVICE, "posterior forward launch failed: %s", hipGetErrorString(err));
     HIP_TRY(hipEventRecord(f1, stream));
     HIP_TRY(hipEventRecord(b0, stream));
@@ -1621,8 +1679,8 @@ cv_opts default_opts() {
 }
 
 // One host-pointer batch call (cv_decode_batch, cv_posterior_batch, cv_kbest_batch,
-// cv_decode_emissions) through the handle's staging buffers; the caller holds h->mu and has
-// selected the device.  stage() checks the caller's arrays and only then enqueues the copies from
+// cv_decode_emissions, cv_posterior_emissions) through the handle's staging buffers; the caller
+// holds h->mu and has selected the device.  stage() checks the caller's arrays and only then enqueues the copies from
 // them; the entry runs its core on the st_* buffers and fetches the results.  obs / path / forced
 // are indexed by absolute element offset: the element slice is [base, total).
 struct HostBatch {
@@ -1663,6 +1721,21 @@ struct HostBatch {
     if (obs && n) HIP_TRY(hipMemcpyAsync(h->st_obs.as<int32_t>() + base, obs + base, n, hipMemcpyHostToDevice, stream));
     if (fr && n) HIP_TRY(hipMemcpyAsync(h->st_forced.as<int32_t>() + base, fr + base, n, hipMemcpyHostToDevice, stream));
     if (fr) o.forced = h->st_forced.as<int32_t>();
+    return CV_OK;
+  }
+  // After stage(): the caller's dense emission rows (cv_decode_emissions, cv_posterior_emissions),
+  // the N scores of each row compact on the device (the columns beyond N are never read).
+  cv_status stage_emis(const double* emis, int64_t ld, EmisSrc* src) {
+    const int64_t N = h->N, rows = total - base;
+    cv_status st = h->st_emis.ensure((size_t)std::max<int64_t>(rows, 1) * N * 8);
+    if (st != CV_OK) return st;
+    if (rows > 0)
+      HIP_TRY(hipMemcpy2DAsync(h->st_emis.p, (size_t)N * 8, emis + base * ld, (size_t)ld * 8, (size_t)N * 8,
+                               (size_t)rows, hipMemcpyHostToDevice, stream));
+    // row e of the staging at p + e * N: the staging holds the elements from `base` on
+    *src = EmisSrc{reinterpret_cast<const double*>(reinterpret_cast<uintptr_t>(h->st_emis.p) -
+                                                   (uintptr_t)base * (uintptr_t)N * 8),
+                   N};
     return CV_OK;
   }
   // a failed core's work is waited for before the caller sees its status
@@ -1781,7 +1854,7 @@ CV_API cv_status cv_hmm_release_workspaces(cv_hmm* h) {
                     &h->chainb.q, &h->chainb.ends, &h->chainb.gid, &h->chainb.gpath, &h->chainb.first,
                     &h->chainb.rpsi, &h->chainb.rows, &h->chainb.small, &h->chainb.rpath, &h->chainb.soff,
                     &h->chainb.sobs, &h->chainb.spath, &h->chainb.sres, &h->chainb.sinit, &h->chainb.slast, &h->ps_rows,
-                    &h->ps_order, &h->st_gamma, &h->kb_bp, &h->kb_last, &h->kb_order, &h->kb_end, &h->st_count,
+                    &h->ps_order, &h->ps_kshift, &h->st_gamma, &h->kb_bp, &h->kb_last, &h->kb_order, &h->kb_end, &h->st_count,
                     &h->st_emis})
     b->release();
   h->ws_rec = false;
@@ -2042,19 +2115,10 @@ CV_API cv_status cv_decode_emissions(cv_hmm* h, int64_t nseq, const int64_t* off
   CV_LOCK(h);
   if ((st = set_device(h)) != CV_OK) return st;
   if (nseq == 0) return CV_OK;
-  const int64_t N = h->N;
   HostBatch hb{h, nseq, offsets, nullptr, o.stream ? (hipStream_t)o.stream : h->stream};
   if ((st = hb.stage(o, 1, 1)) != CV_OK) return st;
-  const int64_t base = hb.base, rows = hb.total - hb.base;
-  if ((st = h->st_emis.ensure((size_t)std::max<int64_t>(rows, 1) * N * 8)) != CV_OK) return st;
-  // the N scores of each row, compact on the device (the columns beyond N are never read)
-  if (rows > 0)
-    HIP_TRY(hipMemcpy2DAsync(h->st_emis.p, (size_t)N * 8, emis + base * ld, (size_t)ld * 8, (size_t)N * 8, (size_t)rows,
-                             hipMemcpyHostToDevice, hb.stream));
-  // row e of the staging at p + e * N: the staging holds the elements from `base` on
-  const EmisSrc src{reinterpret_cast<const double*>(reinterpret_cast<uintptr_t>(h->st_emis.p) -
-                                                    (uintptr_t)base * (uintptr_t)N * 8),
-                    N};
+  EmisSrc src;
+  if ((st = hb.stage_emis(emis, ld, &src)) != CV_OK) return st;
   DecodeReq rq;
   rq.emis = &src;
   st = decode_device(h, nseq, offsets, h->st_off.as<int64_t>(), nullptr, o, h->st_path.as<int32_t>(),
@@ -2064,6 +2128,65 @@ CV_API cv_status cv_decode_emissions(cv_hmm* h, int64_t nseq, const int64_t* off
   hb.fetch_seqs(score_out, h->st_score);
   hb.fetch_seqs(status_out, h->st_status);
   return hb.finish();
+}
+
+// ---- evaluation under caller-supplied emission scores: cv_posterior_emissions* ----------------
+// The checks that need no device, made before any copy from the caller's arrays.
+static cv_status posterior_emissions_args_ok(const cv_hmm* h, int64_t ld, const cv_opts& o) {
+  if (ld < h->N) return set_err(CV_EINVAL, "ld = %lld is less than N = %d", (long long)ld, h->N);
+  return posterior_opts_ok(h, o);
+}
+
+CV_API cv_status cv_posterior_emissions_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
+                                               const int64_t* offsets_dev, const double* emis_dev, int64_t ld,
+                                               const cv_opts* opts, double* loglik_dev, int32_t* path_dev,
+                                               double* gamma_dev, uint8_t* status_dev) {
+  if (!h) return set_err(CV_EINVAL, "null handle");
+  if (nseq < 0) return set_err(CV_EINVAL, "nseq < 0");
+  if (nseq > 0 && (!offsets_dev || !emis_dev || !loglik_dev || !status_dev))
+    return set_err(CV_EINVAL, "null device buffer");
+  const cv_opts o = opts ? *opts : default_opts();
+  cv_status st = posterior_emissions_args_ok(h, ld, o);
+  if (st != CV_OK) return st;
+  CV_LOCK(h);
+  if ((st = set_device(h)) != CV_OK) return st;
+  hipStream_t stream = o.stream ? (hipStream_t)o.stream : h->stream;
+  const EmisSrc src{emis_dev, ld};
+  return posterior_device(h, nseq, offsets_host, offsets_dev, nullptr, o, loglik_dev, path_dev, gamma_dev, status_dev,
+                          stream, &src);
+}
+
+CV_API cv_status cv_posterior_emissions(cv_hmm* h, int64_t nseq, const int64_t* offsets, const double* emis,
+                                        int64_t ld, const cv_opts* opts, double* loglik_out, int32_t* path_out,
+                                        double* gamma_out, uint8_t* status_out) {
+  if (!h) return set_err(CV_EINVAL, "null handle");
+  if (nseq < 0 || (nseq > 0 && (!offsets || !emis || !loglik_out || !status_out)))
+    return set_err(CV_EINVAL, "null argument");
+  cv_opts o = opts ? *opts : default_opts();
+  cv_status st = posterior_emissions_args_ok(h, ld, o);
+  if (st != CV_OK) return st;
+  CV_LOCK(h);
+  if ((st = set_device(h)) != CV_OK) return st;
+  if (nseq == 0) return CV_OK;
+  const int64_t N = h->N;
+  HostBatch hb{h, nseq, offsets, nullptr, o.stream ? (hipStream_t)o.stream : h->stream};
+  if ((st = hb.stage(o, path_out ? 1 : 0, 1)) != CV_OK) return st;
+  if (gamma_out && (st = h->st_gamma.ensure(hb.plane() * (size_t)N * 8)) != CV_OK) return st;
+  EmisSrc src;
+  if ((st = hb.stage_emis(emis, ld, &src)) != CV_OK) return st;
+  st = posterior_device(h, nseq, offsets, h->st_off.as<int64_t>(), nullptr, o, h->st_score.as<double>(),
+                        path_out ? h->st_path.as<int32_t>() : nullptr, gamma_out ? h->st_gamma.as<double>() : nullptr,
+                        h->st_status.as<uint8_t>(), hb.stream, &src);
+  if (st != CV_OK) return hb.fail(st);
+  if (path_out) hb.fetch_elems(path_out, h->st_path);
+  if (gamma_out) hb.fetch_elems(gamma_out, h->st_gamma, (size_t)N);
+  hb.fetch_seqs(loglik_out, h->st_score);
+  hb.fetch_seqs(status_out, h->st_status);
+  if ((st = hb.finish()) != CV_OK) return st;
+  for (int64_t s = 0; s < nseq; ++s)
+    if (status_out[s] == CV_SEQ_INFEASIBLE)
+      return set_err(CV_EINFEASIBLE, "sequence %lld has likelihood 0", (long long)s);
+  return CV_OK;
 }
 
 // ---- consistency-constrained decode --------------------------------------------------------

@@ -35,6 +35,9 @@ struct PostArgs {
   int32_t* path;      // nullable, indexed by element offset
   double* gamma;      // nullable, [element][N]
   double* dump;       // [kPostDumpWaves][64] target of the stores of masked lanes
+  // nullable, [nseq]: the binary exponent the emission rows of each sequence were scaled by
+  // (their sum of k, emis_prepare_lin_f64), added to the forward pass's exponent sum
+  const int64_t* kshift;
 };
 
 // forward pass of the chunk [seq_begin, seq_end): loglik, status, and the rows when g.rows

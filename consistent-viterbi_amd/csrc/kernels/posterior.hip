@@ -13,6 +13,8 @@
 // pass carries sum e as an integer and takes one log10 at the sequence's last element:
 //   loglik = log10(sum_j alpha^_{T-1}[j]) + (sum e) log10(2).
 // gamma_t = alpha^_t o beta^_t / sum(alpha^_t o beta^_t) needs no exponent at all.
+// cv_posterior_emissions*: the emission rows are staged per call, each scaled by its own 2^-k
+// (emis.hip); the sequence's sum k (g.kshift) joins sum e as an integer before that one log10.
 // Every reduction runs in one fixed order (registers over the lane's tiles, DPP over the 16
 // lanes of a row, then the 4 waves through LDS), so runs repeat bit for bit.
 #include <hip/hip_runtime.h>
@@ -204,7 +206,7 @@ __global__ __launch_bounds__(64 * WV, 2) void post_fwd_mm(PostArgs g) {
             const int64_t es = s_es[gi] + e;
             s_es[gi] = es;
             if (!on1)  // the sequence's last element: once per sequence
-              s_ll[gi] = final_loglik(cvf::wsum<WV>(&reds[0][0], G, gi), e, es);
+              s_ll[gi] = final_loglik(cvf::wsum<WV>(&reds[0][0], G, gi), e, es + (g.kshift ? g.kshift[s_seq[gi]] : 0));
           }
           double* arow = g.rows + (size_t)(s_r0[gi] + t) * NP;
 #pragma unroll
@@ -434,7 +436,7 @@ __global__ __launch_bounds__(256) void post_fwd_gen(PostArgs g) {
     const double rmax = cvf::block_max(vm, red);  // its barriers: every read of x is done
     const double rsum = cvf::block_sum(vs, red);
     const int e = row_exp(rmax);
-    if (t == T - 1) ll = final_loglik(rsum, e, esum + e);
+    if (t == T - 1) ll = final_loglik(rsum, e, esum + e + (g.kshift ? g.kshift[s] : 0));
     esum += e;
     double* arow = g.rows ? g.rows + (size_t)(e0 - g.elem_base + t) * NP : nullptr;
     for (int j = tid; j < NP; j += 256) {

@@ -9,6 +9,7 @@ from .decode import (constrained_pairs, constrained_partials, constrained_select
                      decode_constrained, decode_forced_components, decode_superseq_cp, device_memory, last_suffix_traced, last_superseq_stats, last_t64_stats, last_timing, timing_begin,
                      timing_end)
 from .emissions import decode_emissions, decode_emissions_device  # noqa: F401
+from .emissions import posterior_emissions, posterior_emissions_device, score_emissions  # noqa: F401
 from .fit import fit_mle, fit_train  # noqa: F401
 from .kbest import kbest_batch, kbest_batch_device  # noqa: F401
 from .posterior import posterior_batch, posterior_batch_device, score_batch  # noqa: F401

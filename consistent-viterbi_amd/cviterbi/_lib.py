@@ -45,6 +45,7 @@ EXPORTS = [
     "cv_posterior_batch", "cv_posterior_batch_device",
     "cv_kbest_batch", "cv_kbest_batch_device",
     "cv_decode_emissions", "cv_decode_emissions_device",
+    "cv_posterior_emissions", "cv_posterior_emissions_device",
     "cv_last_t64_stats",
 ]
 
@@ -129,6 +130,8 @@ def lib():
         "cv_kbest_batch_device": ([P, I64, P, P, P, I32, P, P, P, P, P], S),
         "cv_decode_emissions": ([P, I64, P, P, I64, P, P, P, P], S),
         "cv_decode_emissions_device": ([P, I64, P, P, P, I64, P, P, P, P], S),
+        "cv_posterior_emissions": ([P, I64, P, P, I64, P, P, P, P, P], S),
+        "cv_posterior_emissions_device": ([P, I64, P, P, P, I64, P, P, P, P, P], S),
         "cv_last_timing": ([P, P], S),
         "cv_timing_begin": ([P], S),
         "cv_timing_end": ([P, P], S),

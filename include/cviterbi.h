@@ -529,6 +529,56 @@ CV_API cv_status cv_decode_emissions_device(cv_hmm* h, int64_t nseq, const int64
                                             const cv_opts* opts, int32_t* path_dev, double* score_dev,
                                             uint8_t* status_dev);
 
+/* ---- evaluation under caller-supplied emission scores -------------------------------------
+ * cv_posterior_batch for the observations of cv_decode_emissions: the handle supplies (pi, A),
+ * its own b is ignored, and emis[e * ld + j] = log10 p(observation of element e | state j),
+ * j < N <= ld, is read as in cv_decode_emissions (rows 8-byte aligned; the device array is read
+ * in place).  loglik_out, path_out (nullable), gamma_out (nullable) and status_out are those of
+ * cv_posterior_batch; both NULL is the scoring mode (forward pass only, no stored rows).
+ * The result is the exact posterior of the discrete model b[j][e] = emis[e][j], obs[e] = e, read
+ * as cv_posterior_batch reads a model, within the bounds below -- not bit-identical to
+ * cv_posterior_batch on that model, because the probability-space rows are built differently:
+ * row e is staged as p[e][j] = 10^emis[e][j] 2^-k_e with the integer k_e that puts the row's
+ * largest entry into [1, 2) (k_e = 0 for a row that is all -inf), and the sequence's sum of k_e
+ * joins the forward pass's integer exponent sum before its single log10.  So any finite
+ * magnitude works -- scores of -5000 per step over thousands of steps, or a lone density of
+ * 10^+40 -- no new rounding enters loglik, and gamma needs nothing (the row scale cancels).
+ * Per entry: -inf is 0 exactly; -0.0 reads as +0.0; an entry more than 300 decades below the
+ * largest of its own row is outside the accuracy contract (it underflows gradually); a NaN, a
+ * +inf or a finite score with |x| >= 2^40 makes its sequence CV_SEQ_BADOBS with the outputs
+ * cv_posterior_batch gives for an out-of-range observation (loglik NaN, path -1, gamma rows 0)
+ * and disturbs no other sequence.  CV_SEQ_INFEASIBLE and CV_SEQ_EMPTY as in cv_posterior_batch;
+ * the host variant returns CV_EINFEASIBLE after writing every output.
+ * Numerics: a staged entry is within c u of 10^x 2^-k_e relative, u = 2^-53, with c = 2: the
+ * worst case of exp10_scaled (csrc/kernels/exp10_scaled.h), one source for host and device with
+ * no math-library call, derived there and pinned against 60-digit arithmetic by the tests
+ * (largest error measured: 1.0 u).  The bounds of cv_posterior_batch hold with N + 8 replaced
+ * by N + 6 + c, i.e. unchanged:
+ *   |loglik - exact| <= 2 T (N + 6 + c) u / ln 10 + 4 T u max(1, S),
+ *   |gamma - exact| <= 4 T (N + 6 + c) u gamma + 1e-290, gamma rows sum to 1 within 4 (N + 6 + c) u.
+ * Results are bit-identical between two calls, between the two variants and under any chunking.
+ * opts as for cv_posterior_batch: dtype CV_DTYPE_F64 (F32: CV_EUNSUPPORTED), assoc
+ * CV_ASSOC_VITERBI (others CV_EINVAL), kernel CV_KERNEL_AUTO or CV_KERNEL_GENERIC, forced;
+ * N <= 4096 (above: CV_EUNSUPPORTED).  ld < N or a null emis is CV_EINVAL.
+ * workspace_bytes caps the forward rows plus the staged emissions and their index of a chunk
+ * (8 NP + 4 bytes per element more; they stay until the chunk's backward pass has run), so the
+ * scoring mode is chunked too (by the staged bytes alone); a single sequence over the cap is
+ * CV_ENOMEM, a sequence of more than INT32_MAX elements CV_ELIMIT.  cv_hmm_release_workspaces
+ * frees them.  cv_last_timing as for cv_posterior_batch; fwd_ms includes the staging kernel.
+ * Host pointers; synchronous. */
+CV_API cv_status cv_posterior_emissions(cv_hmm* h, int64_t nseq, const int64_t* offsets, const double* emis,
+                                        int64_t ld, const cv_opts* opts, double* loglik_out, int32_t* path_out,
+                                        double* gamma_out, uint8_t* status_out);
+/* The same on device-resident buffers, with cv_posterior_batch_device's contract: enqueued on
+ * opts->stream (or the handle's stream), returns after enqueueing (CV_OK where the host variant
+ * reports CV_EINFEASIBLE: read status_dev); offsets_host (nullable) is a host copy of the
+ * offsets; opts->forced is a device pointer.  emis_dev is read in place and must stay valid
+ * until the call has run. */
+CV_API cv_status cv_posterior_emissions_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
+                                               const int64_t* offsets_dev, const double* emis_dev, int64_t ld,
+                                               const cv_opts* opts, double* loglik_dev, int32_t* path_dev,
+                                               double* gamma_dev, uint8_t* status_dev);
+
 /* ---- trait Solver (viterbi_solver.rs:11-16) -------------------------------------------
  * kind: "gpu"      f32 trellis kernel, VITERBI association, f64 re-scored objective
  *       "gpu-f64"  f64, VITERBI association (reference numerics, row A0)
