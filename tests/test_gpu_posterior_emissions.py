@@ -17,7 +17,7 @@ import cviterbi as cv
 from conftest import load_golden
 from cviterbi import _lib as L
 from emis_ref import as_discrete, model, offsets_of
-from test_gpu_posterior import check
+from test_gpu_posterior import check, covering_tags, kernels_of, tag_classes
 from test_posterior import U, gamma_bound, loglik_bound, np_forward_backward, random_model, rowsum_bound
 from test_posterior_emissions import C, FIXTURES
 
@@ -427,3 +427,74 @@ def test_row_shifts(gpu, shift):
             assert rg <= 1.0, (kernel, k, rg)
             worst = max(worst, r, rg)
     print(f"row shifts ({shift}): difference / bound = {worst:.4f}")
+
+
+# ---- partial tags beyond the first column tile / the first 256 states, host and device ------------------
+@pytest.mark.parametrize("N", [130, 300])
+def test_partial_tags_at_every_tile_and_stride(gpu, N):
+    """Tags on states of every column tile, both ends of a DPP row, the last state and (N = 300) a
+    state >= 256 (test_gpu_posterior.tag_classes), as `forced` on the host and `forced_dev` on the device."""
+    pi, a, b0 = model(N)
+    lengths = [12, 1, 5, 2]
+    off = offsets_of(lengths)
+    E = feasible_scores(N, lengths, seed=900 + N)
+    b, obs = as_discrete(E, N)
+    h = cv.HMM(pi, a, b0, device=gpu)
+    path, _, st = cv.decode_emissions(h, off, E)
+    assert np.all(st == L.SEQ_OK)
+    forced = covering_tags(pi, a, b, off, obs, path, tag_classes(N))
+    tagged = np.nonzero(forced >= 0)[0]
+    refs = oracle(pi, a, E, off, forced=forced)
+    E_dev = torch.from_numpy(E).to(f"cuda:{gpu}")
+    worst = 0.0
+    for kernel in kernels_of(N):
+        got = cv.posterior_emissions(h, off, E, forced=forced, gamma=True, kernel=kernel)
+        t = cv.last_timing(h)
+        assert (t["seqs_per_wave"] == 32) == (kernel == "auto" and N <= 256), t
+        worst = max(worst, check(N, off, got, refs, factor=2.0 * factor(N)))
+        onehot = np.zeros((len(tagged), N))
+        onehot[np.arange(len(tagged)), forced[tagged]] = 1.0
+        assert np.array_equal(got[2][tagged], onehot) and np.array_equal(got[1][tagged], forced[tagged]), kernel
+        ll, st = cv.score_emissions(h, off, E, forced=forced, kernel=kernel)
+        assert np.array_equal(ll, got[0]) and np.array_equal(st, got[3])
+        same_bits(on_device(h, off, E_dev, forced=forced, kernel=kernel), got, (N, kernel))
+    print(f"N={N}: tags on states {sorted(set(forced[tagged].tolist()))}, error / (2 x bound) = {worst:.4f}")
+
+
+# ---- output modes: every subset of the outputs is the same computation -----------------------------------
+def test_output_modes_are_bit_identical(gpu):
+    N = 130
+    pi, a, b0, off, E, refs = shape_case(N, 33)
+    h = cv.HMM(pi, a, b0, device=gpu)
+    E_dev = torch.from_numpy(np.array(E)).to(f"cuda:{gpu}")
+    for kernel in ("auto", "generic"):
+        both = cv.posterior_emissions(h, off, E, gamma=True, kernel=kernel)
+        check(N, off, both, refs, factor=2.0 * factor(N))
+        only_path = (both[0], both[1], None, both[3])
+        only_gamma = (both[0], None, both[2], both[3])
+        same_bits(cv.posterior_emissions(h, off, E, gamma=False, kernel=kernel), only_path, (kernel, "path"))
+        same_bits(cv.posterior_emissions(h, off, E, gamma=True, path=False, kernel=kernel), only_gamma, (kernel, "gamma"))
+        same_bits(on_device(h, off, E_dev, gamma=False, kernel=kernel), only_path, (kernel, "device path"))
+        same_bits(on_device(h, off, E_dev, path=False, kernel=kernel), only_gamma, (kernel, "device gamma"))
+        ll, st = cv.score_emissions(h, off, E, kernel=kernel)
+        assert np.array_equal(ll, both[0]) and np.array_equal(st, both[3])
+
+
+# ---- the plain kernels' LDS limit and the widest staging stride ---------------------------------------------
+def test_lds_limit(gpu):
+    """N = 4096: 64 KiB of dynamic LDS in the plain kernels, 16 states per thread, staged rows of NP = 4096."""
+    N = 4096
+    pi, a, b0 = model(N)
+    lengths = [3, 1, 2]
+    off = offsets_of(lengths)
+    E = feasible_scores(N, lengths, seed=4096)
+    refs = oracle(pi, a, E, off)
+    h = cv.HMM(pi, a, b0, device=gpu)
+    got = cv.posterior_emissions(h, off, E, gamma=True)
+    t = cv.last_timing(h)
+    assert t["kernel"] == "generic" and t["padded_states"] == N and t["launches"] == 1, t
+    worst = check(N, off, got, refs, factor=2.0 * factor(N))
+    ll, st = cv.score_emissions(h, off, E)
+    assert np.array_equal(ll, got[0]) and np.array_equal(st, got[3])
+    same_bits(on_device(h, off, torch.from_numpy(E).to(f"cuda:{gpu}")), got, "device")
+    print(f"N={N}: error / (2 x bound) = {worst:.4f}")

@@ -15,7 +15,9 @@ from cviterbi import _lib as L
 
 U = 2.0 ** -53
 FIXTURES = ["posterior_n3.npz", "posterior_n17.npz", "posterior_n64.npz", "posterior_n4_long.npz",
-            "posterior_n4_t4096.npz"]
+            "posterior_n4_t4096.npz", "posterior_n130.npz", "posterior_n250.npz", "posterior_n300.npz"]
+# the fixtures whose tags are partial (the two long ones carry tags on ~30% of 2048 / 4096 elements too)
+TAGGED = FIXTURES[:3] + FIXTURES[5:]
 
 
 # ---- the derived bounds (include/cviterbi.h; DESIGN.md "Posterior") ------------------------------
@@ -118,9 +120,25 @@ def test_numpy_oracle_matches_golden(name):
 
 
 def test_golden_forced_tags_are_partial():
-    for name in FIXTURES[:3]:
+    for name in TAGGED:
         f = load_golden(name)["forced"]
         assert (f >= 0).any() and (f < 0).any()
+
+
+def test_golden_forced_tags_reach_the_later_tiles():
+    """The matrix-core kernels own the states in column tiles of 64 (NP / 64 of them), the plain
+    kernels give thread j the states j, j + 256, ...: the wide fixtures must tag a state beyond the
+    first tile / the first stride, or a regenerated file silently stops testing the mask there."""
+    tags = {}
+    for name in FIXTURES[5:]:
+        z = load_golden(name)
+        f = z["forced"]
+        tags[len(z["pi"])] = f[f >= 0]
+        assert os.path.getsize(os.path.join(ROOT, "tests", "golden", name)) <= 195 * 1024, name
+    assert sorted(tags) == [130, 250, 300]
+    assert (tags[130] >= 64).any() and (tags[130] < 64).any(), tags[130]
+    assert (tags[250] >= 192).any(), tags[250]
+    assert (tags[300] >= 256).any(), tags[300]
 
 
 def test_unscaled_forward_underflows_on_the_long_fixture():

@@ -10,7 +10,7 @@ the free run and for the run with the tags (suffix _f):
   gamma[sum T, N]    P(s_t = j | o)                  rounded to f64
   S[B]               sum_t |log10 c_t|, c_t the per-step normalisers (loglik = sum_t log10 c_t)
 
-    python tools/make_posterior_golden.py
+    python tools/make_posterior_golden.py [fixture names ...]
 """
 from __future__ import annotations
 
@@ -91,9 +91,9 @@ def mp_forward_backward(P, A, B, obs, forced):
     return float(sum(logs)), gamma, float(sum(abs(x) for x in logs))
 
 
-def make(name, n, v, lengths, seed, tag_frac=0.3):
+def make(name, n, v, lengths, seed, tag_frac=0.3, zero_frac=0.1):
     rng = np.random.default_rng(seed)
-    pi, a, b = random_model(rng, n, v)
+    pi, a, b = random_model(rng, n, v, zero_frac)
     offsets = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
     obs = np.zeros(int(offsets[-1]), np.int32)
     forced = np.full(int(offsets[-1]), -1, np.int32)
@@ -125,14 +125,32 @@ def make(name, n, v, lengths, seed, tag_frac=0.3):
     print(f"{name}: N={n} V={v} lengths={list(lengths)} loglik={out['loglik']} ({os.path.getsize(path)} bytes)")
 
 
-def main():
-    make("posterior_n3.npz", 3, 4, [12, 1, 2, 5], seed=301)
-    make("posterior_n17.npz", 17, 5, [33, 1, 7], seed=317)
-    make("posterior_n64.npz", 64, 6, [33, 2], seed=364)
-    make("posterior_n4_long.npz", 4, 8, [2048], seed=304)
-    make("posterior_n4_t4096.npz", 4, 8, [4096], seed=309)
+FIXTURES = {
+    "posterior_n3.npz": dict(n=3, v=4, lengths=[12, 1, 2, 5], seed=301),
+    "posterior_n17.npz": dict(n=17, v=5, lengths=[33, 1, 7], seed=317),
+    "posterior_n64.npz": dict(n=64, v=6, lengths=[33, 2], seed=364),
+    "posterior_n4_long.npz": dict(n=4, v=8, lengths=[2048], seed=304),
+    "posterior_n4_t4096.npz": dict(n=4, v=8, lengths=[4096], seed=309),
+    # beyond one column tile of the matrix-core kernels (NP = 192: 3 tiles, NP = 256: 4) and on the
+    # plain kernels (N > 256); the two sparse models double as a zero-heavy case.  The seeds are
+    # chosen so that the tags reach the later tiles (tests/test_posterior.py asserts it).
+    "posterior_n130.npz": dict(n=130, v=5, lengths=[9, 1, 4], seed=3130, zero_frac=0.1),
+    "posterior_n250.npz": dict(n=250, v=5, lengths=[8, 1, 3], seed=3250, zero_frac=0.75),
+    "posterior_n300.npz": dict(n=300, v=4, lengths=[6, 1, 3], seed=3300, zero_frac=0.8),
+}
+
+
+def main(argv):
+    """No argument: every fixture; else only the named ones (the others stay byte-identical)."""
+    names = argv or list(FIXTURES)
+    for name in names:
+        if name not in FIXTURES:
+            print(f"unknown fixture {name}; known: {' '.join(FIXTURES)}", file=sys.stderr)
+            return 2
+    for name in names:
+        make(name, **FIXTURES[name])
     return 0
 
 
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(main(sys.argv[1:]))
