@@ -258,6 +258,20 @@ struct cv_hmm {
   DevBuf t64_stats;
   PinnedHost t64_stats_pin;
   bool t64_lo_off = false;
+  // certified fixed-point first pass (tuning key t64_fixed_first, fixed_first_decode): the int32
+  // tables in the f32 trellis tables' layouts, built once per handle (fx_state -1: not looked at
+  // yet, 0: the model is outside the pass's range, 1: ready); the per-sequence certificates and
+  // their pinned host copy; the compact batch of the uncertified sequences.  fx_pinned: the
+  // sticky guard -- a call that left more than 1 in 8 sequences uncertified pins the handle to
+  // the f64 kernels.  fx_last: engaged, certified, fallback, pinned (cv_last_fixed_first_stats)
+  int fx_state = -1;
+  DevBuf fx_aimg, fx_pi, fx_et, fx_at;
+  double fx_gain = 0.0;
+  DevBuf fx_cert, fx_idx, fx_obs2, fx_path2, fx_score2, fx_status2;
+  PinnedHost fx_cert_pin;
+  std::vector<int64_t> fx_idx_host;
+  bool fx_pinned = false;
+  int64_t fx_last[4] = {0, 0, 0, 0};
   DevBuf q_pi0;  // the reversed (suffix) pass: pi = 0 for the N states, -inf padding
   // f32 generic tables
   bool g32_ready = false;
@@ -1855,8 +1869,9 @@ CV_API cv_status cv_hmm_release_workspaces(cv_hmm* h) {
                     &h->chainb.rpsi, &h->chainb.rows, &h->chainb.small, &h->chainb.rpath, &h->chainb.soff,
                     &h->chainb.sobs, &h->chainb.spath, &h->chainb.sres, &h->chainb.sinit, &h->chainb.slast, &h->ps_rows,
                     &h->ps_order, &h->ps_kshift, &h->st_gamma, &h->kb_bp, &h->kb_last, &h->kb_order, &h->kb_end, &h->st_count,
-                    &h->st_emis})
+                    &h->st_emis, &h->fx_cert, &h->fx_idx, &h->fx_obs2, &h->fx_path2, &h->fx_score2, &h->fx_status2})
     b->release();
+  h->fx_cert_pin.release();
   h->ws_rec = false;
   h->side.ws_rec = false;
   h->chain_pin.release();
@@ -1927,6 +1942,238 @@ CV_API cv_status cv_hmm_emit_probs(const cv_hmm* h, int64_t obs, double* out) {
   return CV_OK;
 }
 
+// ---- certified fixed-point first pass of the exact f64 batch decode -------------------------
+// (tuning key t64_fixed_first; DESIGN.md "Certified fixed-point first pass")
+static int32_t fix_quantise(double x) {  // max(rint(x / q), F); -inf -> F.  x <= 0
+  const double r = std::nearbyint(std::ldexp(x, -cvk::kFixQLog2));
+  return r > (double)cvk::kFixFloor ? (int32_t)r : cvk::kFixFloor;
+}
+
+// The int32 tables, once per handle.  fx_state = 0: the model is outside the pass's range (a
+// positive entry, or a padded state count the integer pair kernel does not cover).
+static cv_status ensure_fix_tables(cv_hmm* h) {
+  if (h->fx_state >= 0) return CV_OK;
+  const int np = cvk::trellis_padded_states(h->N);
+  if (!cvk::fix_supported(np) || !model_nonpos(h)) {
+    h->fx_state = 0;
+    return CV_OK;
+  }
+  const int N = h->N;
+  const int64_t V = h->V;
+  const int R = np / 8;
+  const int32_t F = cvk::kFixFloor;
+  auto A = [&](int i, int j) -> int32_t { return (i < N && j < N) ? fix_quantise(h->a[(size_t)i * N + j]) : F; };
+  std::vector<int32_t> img((size_t)np * np), pi((size_t)np, F), at((size_t)np * np, F), et((size_t)V * np, F);
+  for (int w = 0; w < np / 16; ++w)  // the register image of ensure_trellis_tables
+    for (int q = 0; q < R / 2; ++q)
+      for (int lane = 0; lane < 64; ++lane) {
+        const int rg = lane & 7, cp = lane >> 3, j0 = 16 * w + 2 * cp, r0 = rg * R + 2 * q;
+        int32_t* dst = &img[(((size_t)w * (R / 2) + q) * 64 + lane) * 4];
+        dst[0] = A(r0, j0);
+        dst[1] = A(r0, j0 + 1);
+        dst[2] = A(r0 + 1, j0);
+        dst[3] = A(r0 + 1, j0 + 1);
+      }
+  for (int j = 0; j < N; ++j) pi[(size_t)j] = fix_quantise(h->pi[(size_t)j]);
+  for (int i = 0; i < N; ++i)
+    for (int j = 0; j < N; ++j) at[(size_t)j * np + i] = A(i, j);
+  parallel_ranges(N, [&](int, int64_t lo, int64_t hi) {
+    for (int64_t j = lo; j < hi; ++j)
+      for (int64_t o = 0; o < V; ++o) et[(size_t)o * np + j] = fix_quantise(h->b[(size_t)j * V + o]);
+  }, std::max<int64_t>(1, 4096 / std::max<int64_t>(V, 1)));
+  // the f64 recurrence's own rounding, which a certificate has to cover besides the quantisation:
+  // at step t at most 2.02 u (t + 1) W, W = the largest finite |pi| + |a| + |b|; in units of q and
+  // summed over the steps it stays below gain * (t + 1)^2
+  double wmax = 0.0;
+  for (const std::vector<double>* v : {&h->pi, &h->a, &h->b}) {
+    double m = 0.0;
+    for (double x : *v)
+      if (std::isfinite(x)) m = std::max(m, std::fabs(x));
+    wmax += m;
+  }
+  h->fx_gain = 1.01 * 2.02 * std::ldexp(1.0, -53 - cvk::kFixQLog2) * wmax;
+  cv_status st;
+  if ((st = upload(h->fx_aimg, img.data(), img.size() * 4)) != CV_OK) return st;
+  if ((st = upload(h->fx_pi, pi.data(), pi.size() * 4)) != CV_OK) return st;
+  if ((st = upload(h->fx_at, at.data(), at.size() * 4)) != CV_OK) return st;
+  if ((st = upload(h->fx_et, et.data(), et.size() * 4)) != CV_OK) return st;
+  h->fx_state = 1;
+  return CV_OK;
+}
+
+// The plain row-A0 f64 batch decode through the integer pass.  *done = false: the call is not
+// the pass's (options, model, batch size, the handle's guard) and nothing has been written; the
+// caller runs the f64 kernels.  Otherwise every sequence has its result: the certified ones from
+// the integer rows (path) and the f64 fold along it (score), the others -- uncertified, unpaired,
+// empty, with a bad observation -- from the f64 kernels on a compact batch, scattered back.  The
+// uncertified list is read on the host, so the call waits for the stream once.
+static cv_status fixed_first_decode(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, const int64_t* offsets_dev,
+                                    const int32_t* obs_dev, const cv_opts& o, int32_t* path_dev, double* score_dev,
+                                    uint8_t* status_dev, hipStream_t stream, bool* done) {
+  *done = false;
+  h->fx_last[0] = h->fx_last[1] = h->fx_last[2] = 0;
+  h->fx_last[3] = h->fx_pinned ? 1 : 0;
+  const int64_t min_elems = h->tuning.t64_fixed_first;
+  if (min_elems <= 0 || h->fx_pinned || h->fx_state == 0 || nseq < 2 || nseq > INT32_MAX) return CV_OK;
+  if (o.dtype != CV_DTYPE_F64 || o.assoc != CV_ASSOC_VITERBI || o.forced || o.flags != 0 ||
+      (o.kernel != CV_KERNEL_AUTO && o.kernel != CV_KERNEL_TRELLIS_F64))
+    return CV_OK;
+  std::vector<int64_t> off_copy;
+  cv_status st = host_offsets(nseq, offsets_host, offsets_dev, off_copy, stream);
+  if (st != CV_OK) return st;
+  if (offsets_host[nseq] - offsets_host[0] < min_elems) return CV_OK;
+  if ((st = ensure_fix_tables(h)) != CV_OK) return st;
+  if (h->fx_state != 1) return CV_OK;
+  if ((st = ensure_f64_tables(h)) != CV_OK) return st;
+  const int np = cvk::trellis_padded_states(h->N);
+
+  // chunks of whole sequences under the workspace cap, 4 * np bytes of rows per element; inside a
+  // chunk equal-length neighbours of the longest-first order are paired, the leftovers fall back
+  const uint64_t per_elem = (uint64_t)np * 4;
+  const uint64_t cap = o.workspace_bytes ? o.workspace_bytes : default_workspace_cap(h->ws_main.bytes, kDefaultWorkspaceT64);
+  std::vector<cvplan::Chunk> chunks;
+  cvplan::split_pipelined(offsets_host, nseq, {per_elem, cap, true, 8, 2 * (int64_t)std::max(h->cus, 1)}, chunks);
+  const cvplan::Shares largest = cvplan::measure(offsets_host, chunks);
+  if ((st = h->ws_main.ensure(std::max<uint64_t>(largest.max_elems, 1) * per_elem)) != CV_OK) return st;
+  if ((st = h->fx_cert.ensure((size_t)nseq)) != CV_OK) return st;
+  if (!h->fx_cert_pin.ensure((size_t)nseq)) return set_err(CV_ENOMEM, "pinned certificate copy failed");
+  if (h->ws_rec) HIP_TRY(hipStreamWaitEvent(stream, h->ws_done, 0));
+  const bool varlen = cvplan::varlen(offsets_host, nseq);
+  std::vector<int64_t> npair(chunks.size(), 0);
+  const int32_t* order_dev = nullptr;
+  if (varlen) {
+    h->order_host.resize((size_t)nseq);
+    cvplan::longest_first(offsets_host, chunks, h->order_host.data(), npair.data(), h->sort_pos);
+    if ((st = upload_order(h->ws_order, h->order_pin, h->order_host.data(), nseq, stream, &order_dev)) != CV_OK) return st;
+  }
+  HIP_TRY(hipMemsetAsync(h->fx_cert.p, 0, (size_t)nseq, stream));
+
+  // this call's launches -- the integer chunks, then the fallback's -- are timed as one call
+  const bool acc_was = h->acc_on;
+  const size_t acc_base = acc_was ? h->acc_used : 0;
+  if (!acc_was) h->acc_on = true, h->acc_used = 0;
+  struct AccRestore {
+    cv_hmm* h;
+    bool was;
+    ~AccRestore() {
+      if (!was) h->acc_on = false, h->acc_used = 0;
+    }
+  } acc_restore{h, acc_was};
+  const size_t nev = 4 * chunks.size();
+  size_t eb;
+  if ((st = reserve_events(h, false, nev, &eb)) != CV_OK) return st;
+  for (size_t ci = 0; ci < chunks.size(); ++ci) {
+    const cvplan::Chunk c = chunks[ci];
+    const int64_t n = c.second - c.first;
+    const int64_t np2 = varlen ? npair[ci] : n / 2;
+    HIP_TRY(hipEventRecord(h->ev[eb + 4 * ci], stream));
+    cvk::FixFwdArgs fa{};
+    fa.a_img = h->fx_aimg.as<int32_t>();
+    fa.pi = h->fx_pi.as<int32_t>();
+    fa.et = h->fx_et.as<int32_t>();
+    fa.offsets = offsets_dev;
+    fa.obs = obs_dev;
+    fa.order = order_dev;
+    fa.seq_begin = c.first;
+    fa.rows = h->ws_main.as<int32_t>();
+    fa.row_elem_base = offsets_host[c.first];
+    fa.cert = h->fx_cert.as<uint8_t>();
+    fa.nobs = (int)h->V;
+    hipError_t err = cvk::launch_fix_fwd2(np, fa, np2, stream);
+    if (err != hipSuccess) return set_err(CV_EDEVICE, "fixed-point forward launch failed: %s", hipGetErrorString(err));
+    HIP_TRY(hipEventRecord(h->ev[eb + 4 * ci + 1], stream));
+    HIP_TRY(hipEventRecord(h->ev[eb + 4 * ci + 2], stream));
+    cvk::FixBtArgs ba{};
+    ba.rows = fa.rows;
+    ba.row_elem_base = fa.row_elem_base;
+    ba.at = h->fx_at.as<int32_t>();
+    ba.offsets = offsets_dev;
+    ba.order = order_dev;
+    ba.seq_begin = c.first;
+    ba.seq_end = c.first + 2 * np2;  // the paired slots: only their rows exist
+    ba.gain = h->fx_gain;
+    ba.path = path_dev;
+    ba.cert = fa.cert;
+    err = cvk::launch_fix_bt(np, ba, stream);
+    if (err == hipSuccess) {
+      cvk::FixScoreArgs ra{};
+      ra.path = path_dev;
+      ra.obs = obs_dev;
+      ra.offsets = offsets_dev;
+      ra.seq_begin = c.first;
+      ra.seq_end = c.second;
+      ra.nstates = h->N;
+      ra.pi64 = h->d_pi64.as<double>();
+      ra.a64 = h->d_a64.as<double>();
+      ra.et64 = h->d_et64.as<double>();
+      ra.cert = fa.cert;
+      ra.score = score_dev;
+      ra.status = status_dev;
+      err = cvk::launch_fix_score(ra, stream);
+    }
+    if (err != hipSuccess) return set_err(CV_EDEVICE, "fixed-point backtrack launch failed: %s", hipGetErrorString(err));
+    HIP_TRY(hipEventRecord(h->ev[eb + 4 * ci + 3], stream));
+  }
+  if ((st = end_call(h, false, nev, stream)) != CV_OK) return st;
+  HIP_TRY(hipMemcpyAsync(h->fx_cert_pin.p, h->fx_cert.p, (size_t)nseq, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+
+  const uint8_t* cert = h->fx_cert_pin.as<uint8_t>();
+  std::vector<int64_t>& ix = h->fx_idx_host;  // cstart [nfb], off2 [nfb + 1], perm [nfb]
+  int64_t nfb = 0, nfail = 0;  // not certified; of them, the pass ran to a failed certificate (2)
+  for (int64_t s = 0; s < nseq; ++s) nfb += cert[s] != 1, nfail += cert[s] == 2;
+  h->fx_last[0] = 1;
+  h->fx_last[1] = nseq - nfb;
+  h->fx_last[2] = nfb;
+  h->fx_last[3] = 0;
+  if (nfail * 8 > nseq - nfb + nfail) {  // the guard: this model's margins are below the quantisation; f64 from now on
+    h->fx_pinned = true;
+    h->fx_last[1] = 0, h->fx_last[2] = nseq, h->fx_last[3] = 1;
+    if (acc_was) h->acc_used = acc_base;  // the f64 decode of the whole batch is what the call reports
+    return CV_OK;
+  }
+  *done = true;
+  h->last_kernel = CV_KERNEL_TRELLIS_F64;
+  h->last_np = np;
+  h->last_mt = 2;
+  if (nfb > 0) {
+    ix.resize((size_t)(3 * nfb + 1));
+    int64_t *cstart = ix.data(), *off2 = cstart + nfb, *perm = off2 + nfb + 1;
+    int64_t k = 0;
+    off2[0] = 0;
+    for (int64_t s = 0; s < nseq; ++s)
+      if (cert[s] != 1) {
+        cstart[k] = offsets_host[s];
+        off2[k + 1] = off2[k] + (offsets_host[s + 1] - offsets_host[s]);
+        perm[k++] = s;
+      }
+    const int64_t elems2 = off2[nfb];
+    if ((st = h->fx_idx.ensure(ix.size() * 8)) != CV_OK) return st;
+    if ((st = h->fx_obs2.ensure((size_t)std::max<int64_t>(elems2, 1) * 4)) != CV_OK) return st;
+    if ((st = h->fx_path2.ensure((size_t)std::max<int64_t>(elems2, 1) * 4)) != CV_OK) return st;
+    if ((st = h->fx_score2.ensure((size_t)nfb * 8)) != CV_OK) return st;
+    if ((st = h->fx_status2.ensure((size_t)nfb)) != CV_OK) return st;
+    HIP_TRY(hipMemcpyAsync(h->fx_idx.p, ix.data(), ix.size() * 8, hipMemcpyHostToDevice, stream));
+    const int64_t *d_cstart = h->fx_idx.as<int64_t>(), *d_off2 = d_cstart + nfb, *d_perm = d_off2 + nfb + 1;
+    hipError_t err = cvk::launch_compact_suffix(d_cstart, d_off2, obs_dev, nullptr, nullptr, h->fx_obs2.as<int32_t>(),
+                                                nullptr, nfb, stream);
+    if (err != hipSuccess) return set_err(CV_EDEVICE, "fallback gather launch failed: %s", hipGetErrorString(err));
+    DecodeReq rq;
+    rq.batch_api = true;
+    if ((st = decode_device(h, nfb, off2, d_off2, h->fx_obs2.as<int32_t>(), o, h->fx_path2.as<int32_t>(),
+                            h->fx_score2.as<double>(), h->fx_status2.as<uint8_t>(), stream, rq)) != CV_OK)
+      return st;
+    err = cvk::launch_scatter_suffix(d_cstart, d_off2, d_perm, h->fx_path2.as<int32_t>(), h->fx_score2.as<double>(),
+                                     h->fx_status2.as<uint8_t>(), path_dev, score_dev, status_dev, nfb, stream);
+    if (err != hipSuccess) return set_err(CV_EDEVICE, "fallback scatter launch failed: %s", hipGetErrorString(err));
+    // the fallback's buffers are read by the scatter: the next call on the handle waits for it
+    if ((st = end_call(h, false, 0, stream)) != CV_OK) return st;
+  }
+  h->last_ev_base = acc_base;
+  h->last_launches = (int64_t)((h->acc_used - acc_base) / 4);
+  return CV_OK;
+}
+
 CV_API cv_status cv_decode_batch_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
                                         const int64_t* offsets_dev, const int32_t* obs_dev, const cv_opts* opts,
                                         int32_t* path_dev, double* score_dev, uint8_t* status_dev) {
@@ -1938,6 +2185,9 @@ CV_API cv_status cv_decode_batch_device(cv_hmm* h, int64_t nseq, const int64_t* 
   if (st != CV_OK) return st;
   const cv_opts o = opts ? *opts : default_opts();
   hipStream_t stream = o.stream ? (hipStream_t)o.stream : h->stream;
+  bool done = false;
+  st = fixed_first_decode(h, nseq, offsets_host, offsets_dev, obs_dev, o, path_dev, score_dev, status_dev, stream, &done);
+  if (st != CV_OK || done) return st;
   DecodeReq rq;
   rq.batch_api = true;
   return decode_device(h, nseq, offsets_host, offsets_dev, obs_dev, o, path_dev, score_dev, status_dev, stream, rq);
@@ -1955,8 +2205,14 @@ static cv_status decode_host_locked(cv_hmm* h, int64_t nseq, const int64_t* offs
   if ((st = hb.stage(o, 1, 1, true, !forced_staged)) != CV_OK) return st;
   DecodeReq rq;
   rq.batch_api = batch_api;
-  st = decode_device(h, nseq, offsets, h->st_off.as<int64_t>(), h->st_obs.as<int32_t>(), o, h->st_path.as<int32_t>(),
-                     h->st_score.as<double>(), h->st_status.as<uint8_t>(), hb.stream, rq);
+  bool done = false;
+  if (batch_api && !forced_staged)
+    st = fixed_first_decode(h, nseq, offsets, h->st_off.as<int64_t>(), h->st_obs.as<int32_t>(), o,
+                            h->st_path.as<int32_t>(), h->st_score.as<double>(), h->st_status.as<uint8_t>(), hb.stream,
+                            &done);
+  if (st == CV_OK && !done)
+    st = decode_device(h, nseq, offsets, h->st_off.as<int64_t>(), h->st_obs.as<int32_t>(), o, h->st_path.as<int32_t>(),
+                       h->st_score.as<double>(), h->st_status.as<uint8_t>(), hb.stream, rq);
   if (st != CV_OK) return hb.fail(st);
   hb.fetch_elems(path_out, h->st_path);
   hb.fetch_seqs(score_out, h->st_score);
@@ -3589,6 +3845,15 @@ CV_API int32_t cv_last_t64_stats(const cv_hmm* h, int64_t* out, int32_t n) {
   t64_stats_sum(h, v);
   for (int32_t q = 0; q < n && q < 8; ++q) out[q] = v[q];
   return 8;
+}
+
+CV_API int32_t cv_last_fixed_first_stats(const cv_hmm* h, int64_t* out, int32_t n) {
+  if (!h || n < 0 || (n > 0 && !out)) {
+    set_err(CV_EINVAL, "bad argument");
+    return -1;
+  }
+  for (int32_t q = 0; q < n && q < 4; ++q) out[q] = h->fx_last[q];
+  return 4;
 }
 
 CV_API cv_status cv_last_suffix_traced(const cv_hmm* h, int64_t* out) {

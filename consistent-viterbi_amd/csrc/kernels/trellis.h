@@ -76,6 +76,53 @@ struct RescoreArgs {
 };
 hipError_t launch_rescore_f64(const RescoreArgs& r, int64_t nseq, hipStream_t stream, int lds_reserve = 0);
 
+// Certified fixed-point first pass of the exact f64 decode (trellis_fwd2_i32, backtrack_fix_i32,
+// fix_score_f64): int32 tables in units of q = 2^kFixQLog2 log10 units, floored at kFixFloor, in
+// the layouts of the f32 trellis tables (a_img, pi, et, at at the padded stride).
+constexpr int kFixQLog2 = -26;
+constexpr int32_t kFixFloor = -(1 << 30);
+struct FixFwdArgs {
+  const int32_t* a_img;
+  const int32_t* pi;
+  const int32_t* et;
+  const int64_t* offsets;
+  const int32_t* obs;
+  const int32_t* order;    // optional schedule: slot -> sequence id
+  int64_t seq_begin;       // slots seq_begin + 2k, + 2k + 1 hold a pair of equal length
+  int32_t* rows;           // [(elements of chunk)][NP]
+  int64_t row_elem_base;
+  uint8_t* cert;           // [nseq_total], zeroed: CVK_SEQ_BADOBS where an observation is out of range
+  int nobs;
+};
+struct FixBtArgs {
+  const int32_t* rows;
+  int64_t row_elem_base;
+  const int32_t* at;
+  const int64_t* offsets;
+  const int32_t* order;
+  int64_t seq_begin, seq_end;  // slots
+  double gain;             // the f64 recurrence's rounding per squared step, in units of q
+  int32_t* path;
+  uint8_t* cert;           // 0 -> 1 where the path is certified (its path is then written), 0 -> 2 where not
+};
+struct FixScoreArgs {
+  const int32_t* path;
+  const int32_t* obs;
+  const int64_t* offsets;
+  int64_t seq_begin, seq_end;  // sequences
+  int nstates;
+  const double* pi64;
+  const double* a64;
+  const double* et64;
+  uint8_t* cert;           // 1 -> 2 where a floored pi / b entry lies on the path
+  double* score;           // written with status OK where cert stays 1
+  uint8_t* status;
+};
+bool fix_supported(int np);
+hipError_t launch_fix_fwd2(int np, const FixFwdArgs& fa, int64_t npairs, hipStream_t stream);
+hipError_t launch_fix_bt(int np, const FixBtArgs& ba, hipStream_t stream);
+hipError_t launch_fix_score(const FixScoreArgs& r, hipStream_t stream);
+
 template <typename REAL>
 struct GenericFwdArgs {
   const int32_t* forced;   // [sum T] nullable: -1 free, else forced state

@@ -903,6 +903,348 @@ __global__ __launch_bounds__(256) void backtrack_v_f32(BacktrackArgs args) {
 }
 
 // ---------------------------------------------------------------------------------
+// Certified fixed-point first pass of the exact f64 decode (DESIGN.md "Certified fixed-point
+// first pass"; tools/probe_fixed_first.py is the numpy model these kernels follow step by step).
+// The tables are int32 multiples of q = 2^kFixQLog2 log10 units, floored at kFixFloor (-inf and
+// the padding map to the floor); every table entry is <= 0, so every value below is in
+// [2 * kFixFloor, 0] and no int32 operation can overflow.
+//   trellis_fwd2_i32   trellis_fwd2_f32's layout (two sequences per workgroup, A register
+//                      resident, one barrier per step) on integers: one v_add_u32 and half a
+//                      v_max3_i32 per pair.  Row t is stored minus the maximum of row t-1 (each
+//                      wave folds its 16 columns' maximum and one lane posts it with an LDS
+//                      atomic max; the next step of that sequence reads it after the barrier),
+//                      so the rows stay inside the 2^30 window for any T.
+//   backtrack_fix_i32  one wave per sequence: first argmax and the largest other candidate at
+//                      every step; the sequence is certified when every gap covers the
+//                      quantisation and rounding bound of that step and no winner is at the floor.
+//   fix_score_f64      one lane per certified sequence: the f64 fold along the path (the f64
+//                      recurrence's own value there), and the check that no pi / b entry on the
+//                      path was floored.
+__device__ __forceinline__ int dppi_max_mirror(int mine, int other) {
+  asm volatile("s_nop 1\n\tv_max_i32_dpp %0, %1, %0 row_half_mirror row_mask:0xf bank_mask:0xf"
+               : "+v"(mine)
+               : "v"(other));
+  return mine;
+}
+__device__ __forceinline__ int dppi_max_xor1(int x) {
+  asm volatile("s_nop 1\n\tv_max_i32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" : "+v"(x));
+  return x;
+}
+__device__ __forceinline__ int dppi_max_xor2(int x) {
+  asm volatile("s_nop 1\n\tv_max_i32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf" : "+v"(x));
+  return x;
+}
+__device__ __forceinline__ int dppi_max_half_mirror(int x) {
+  asm volatile("s_nop 1\n\tv_max_i32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf" : "+v"(x));
+  return x;
+}
+// max over the 16 lanes of a row given octets that already agree, then over the four rows
+__device__ __forceinline__ int rows_max_i(int x) {
+  asm volatile("s_nop 1\n\tv_max_i32_dpp %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf" : "+v"(x));
+  int a = x, b = x;
+  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+  x = max(a, b);
+  a = x, b = x;
+  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+  return max(a, b);
+}
+__device__ __forceinline__ int wave_max_i(int x) {
+  return rows_max_i(dppi_max_half_mirror(dppi_max_xor2(dppi_max_xor1(x))));
+}
+
+template <int NP>
+__global__ __launch_bounds__(NP * 4) void trellis_fwd2_i32(FixFwdArgs args) {
+  using G = TrellisGeom<NP>;
+  constexpr int R = G::R;
+  constexpr int S = G::S;
+  constexpr int F = kFixFloor;
+  static_assert(R % 8 == 0, "pair kernel needs NP % 64 == 0");
+  __shared__ __attribute__((aligned(16))) int lds[2][2][G::LDS_FLOATS];  // [X/Y][buffer]
+  __shared__ int mu[2][3];  // [X/Y][t % 3]: the maximum of row t
+
+  const int lane = threadIdx.x & 63;
+  const int w = threadIdx.x >> 6;
+  const int rg = lane & 7;
+  const int cp = lane >> 3;
+  const int j0 = 16 * w + 2 * cp;
+  const bool hi = rg >= 4;  // column of this lane after the fold: j0 + hi
+  const unsigned jw = (unsigned)(j0 + (hi ? 1 : 0));
+
+  const int64_t slot = args.seq_begin + 2 * (int64_t)blockIdx.x;
+  const int64_t seqX = args.order ? (int64_t)args.order[slot] : slot;
+  const int64_t seqY = args.order ? (int64_t)args.order[slot + 1] : slot + 1;
+  const int64_t eX = args.offsets[seqX], eY = args.offsets[seqY];
+  const int T = (int)(args.offsets[seqX + 1] - eX);  // the host pairs equal lengths
+  if (T <= 0) return;
+  typedef const __attribute__((address_space(4))) int32_t* cobs_t;
+  const cobs_t obsX = (cobs_t)(args.obs + eX);
+  const cobs_t obsY = (cobs_t)(args.obs + eY);
+  int32_t* const dX = args.rows + (eX - args.row_elem_base) * NP;  // uniform row bases
+  int32_t* const dY = args.rows + (eY - args.row_elem_base) * NP;
+  const unsigned V = (unsigned)args.nobs;
+
+  if (threadIdx.x < 6) (&mu[0][0])[threadIdx.x] = INT32_MIN;
+  int a_reg[2 * R];
+  {
+    const int4* img = reinterpret_cast<const int4*>(args.a_img) + (size_t)w * (R / 2) * 64 + lane;
+#pragma unroll
+    for (int q = 0; q < R / 2; ++q) {
+      const int4 v = img[q * 64];
+      a_reg[4 * q + 0] = v.x;
+      a_reg[4 * q + 1] = v.y;
+      a_reg[4 * q + 2] = v.z;
+      a_reg[4 * q + 3] = v.w;
+    }
+  }
+  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the A image is resident before the step loop
+  unsigned bad = 0;                    // bit 0: X, bit 1: Y
+  auto obs_x = [&](int t) -> unsigned {
+    const unsigned o = (unsigned)obsX[t];
+    bad |= (o >= V) ? 1u : 0u;
+    return o < V ? o : 0u;
+  };
+  auto obs_y = [&](int t) -> unsigned {
+    const unsigned o = (unsigned)obsY[t];
+    bad |= (o >= V) ? 2u : 0u;
+    return o < V ? o : 0u;
+  };
+  auto et_row = [&](unsigned o) -> int { return (args.et + (size_t)o * NP)[jw]; };
+  const int lds_w = (j0 / R) * S + (j0 % R) + (hi ? 1 : 0);
+  auto clampT = [&](int t) { return t < T ? t : T - 1; };
+  // the row maximum: one DPP level folds an octet's two columns, then one lane per octet posts it
+  // with an LDS atomic max (128 per row; the LDS pipe has the room, the VALU does not).  Inline
+  // asm: the compiler's atomic optimiser would put a wave reduction in front of the builtin.  The
+  // op is not in the compiler's lgkmcnt count, which only makes its own waits stricter, and
+  // lds_barrier waits for lgkmcnt(0) before the barrier that publishes the maximum.
+  typedef __attribute__((address_space(3))) int* lds_int_t;
+  auto post_max = [&](int v, int* dst) {
+    const int m = dppi_max_half_mirror(v);
+    if (rg == 0) asm volatile("ds_max_i32 %0, %1" : : "v"((unsigned)(size_t)(lds_int_t)dst), "v"(m) : "memory");
+  };
+  lds_barrier();  // mu initialised
+
+  {  // t = 0 for both sequences
+    const int ex = et_row(obs_x(0)), ey = et_row(obs_y(0));
+    const int p = args.pi[jw];
+    const int dx = max(p + ex, F), dy = max(p + ey, F);
+    lds[0][0][lds_w] = dx;
+    lds[1][0][lds_w] = dy;
+    dX[jw] = dx;
+    dY[jw] = dy;
+    post_max(dx, &mu[0][0]);
+    post_max(dy, &mu[1][0]);
+  }
+  int eXr = et_row(obs_x(clampT(1)));  // X at t = 1
+  int eYr;
+  unsigned oY = obs_y(clampT(1));
+  unsigned oX = obs_x(clampT(2));
+  lds_barrier();
+  constexpr int KB = R / 8;  // 8-row blocks per lane
+  auto ld8 = [&](const int* src, int4 (&dst)[2]) {
+    dst[0] = *reinterpret_cast<const int4*>(src);
+    dst[1] = *reinterpret_cast<const int4*>(src + 4);
+  };
+  int4 P[2], Q[2];
+  ld8(&lds[0][0][rg * S], P);
+
+  // One half-step at step t (trellis_fwd2_f32's, one barrier per step: it follows the X half).
+  // mus = this sequence's mu slots.
+  auto half = [&](const int* dsrc, const int* nsrc, int* ldst, int32_t* drow, int* mus, int t, const int& e_use,
+                  int& e_load, unsigned& o_load, bool first, int t_obs) {
+    e_load = et_row(o_load);
+    const int mu_use = mus[(t + 2) % 3];  // the maximum of row t-1
+    if (threadIdx.x == 0) mus[(t + 1) % 3] = INT32_MIN;
+    if (KB > 1) ld8(dsrc + 8, Q);
+    int m0a = 0, m0b = 0, m1a = 0, m1b = 0;
+    auto rows4 = [&](const int4& dd, int k, bool init) {
+      const int s00 = dd.x + a_reg[2 * k + 0], s01 = dd.x + a_reg[2 * k + 1];
+      const int s10 = dd.y + a_reg[2 * k + 2], s11 = dd.y + a_reg[2 * k + 3];
+      const int s20 = dd.z + a_reg[2 * k + 4], s21 = dd.z + a_reg[2 * k + 5];
+      const int s30 = dd.w + a_reg[2 * k + 6], s31 = dd.w + a_reg[2 * k + 7];
+      if (init) {
+        m0a = max(s00, s10);
+        m1a = max(s01, s11);
+        m0b = max(s20, s30);
+        m1b = max(s21, s31);
+      } else {
+        m0a = max(max(m0a, s00), s10);
+        m1a = max(max(m1a, s01), s11);
+        m0b = max(max(m0b, s20), s30);
+        m1b = max(max(m1b, s21), s31);
+      }
+    };
+#pragma unroll
+    for (int k = 0; k < KB; ++k) {
+      int4(&B)[2] = (k & 1) ? Q : P;
+      rows4(B[0], 8 * k, k == 0);
+      rows4(B[1], 8 * k + 4, false);
+      __builtin_amdgcn_sched_barrier(0);
+      if (k + 2 < KB)
+        ld8(dsrc + 8 * (k + 2), B);
+      else if (!(k & 1) && (k + 2 == KB || k + 1 == KB) && !first)
+        ld8(nsrc, P);  // next half-step's block 0
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    const int m0 = max(m0a, m0b);
+    const int m1 = max(m1a, m1b);
+    int m = dppi_max_mirror(hi ? m1 : m0, hi ? m0 : m1);
+    m = dppi_max_xor1(m);
+    m = dppi_max_xor2(m);
+    const int dn = max((max(m, F) + e_use) - mu_use, F);
+    __builtin_amdgcn_sched_barrier(0);
+    o_load = first ? obs_y(t_obs) : obs_x(t_obs);
+    ldst[lds_w] = dn;
+    (drow + (size_t)t * NP)[jw] = dn;
+    post_max(dn, &mus[t % 3]);
+    if (first) {
+      lds_barrier();
+      ld8(nsrc, P);  // Y's delta_{t-1}, complete since the barrier
+    }
+  };
+  auto step = [&](int t) {
+    const int cur = (t - 1) & 1, nxt = t & 1;
+    half(&lds[0][cur][rg * S], &lds[1][cur][rg * S], &lds[0][nxt][0], dX, mu[0], t, eXr, eYr, oY, true, clampT(t + 1));
+    half(&lds[1][cur][rg * S], &lds[0][nxt][rg * S], &lds[1][nxt][0], dY, mu[1], t, eYr, eXr, oX, false, clampT(t + 2));
+  };
+  for (int t = 1; t < T; ++t) step(t);
+  if (bad && lane == 0 && w == 0) {
+    if (bad & 1u) args.cert[seqX] = CVK_SEQ_BADOBS;
+    if (bad & 2u) args.cert[seqY] = CVK_SEQ_BADOBS;
+  }
+}
+
+template <int NP>
+__global__ __launch_bounds__(256) void backtrack_fix_i32(FixBtArgs args) {
+  constexpr int VL = NP / 64;
+  constexpr int PF = 8;
+  constexpr int F = kFixFloor;
+  static_assert(VL == 4, "int4 rows");
+  const int lane = threadIdx.x & 63;
+  const int64_t slot = args.seq_begin + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (slot >= args.seq_end) return;
+  const int64_t seq = args.order ? (int64_t)args.order[slot] : slot;
+  const int64_t e0 = args.offsets[seq];
+  const int T = (int)(args.offsets[seq + 1] - e0);
+  if (T <= 0 || args.cert[seq] != 0) return;  // empty, bad observation: the f64 decode's business
+  int32_t* __restrict__ path = args.path + e0;
+  const int32_t* __restrict__ drow = args.rows + (e0 - args.row_elem_base) * NP + VL * lane;
+  const int32_t* __restrict__ at = args.at + VL * lane;
+  const double g = args.gain;
+  auto extra = [&](int n) { return (long long)fmin(floor(g * (double)n * (double)n), 536870912.0); };
+  auto load_row = [&](int r, int (&dst)[VL]) {
+    if (r >= 0) {
+      const int4 x = *reinterpret_cast<const int4*>(drow + (size_t)r * NP);
+      dst[0] = x.x, dst[1] = x.y, dst[2] = x.z, dst[3] = x.w;
+    } else {
+      dst[0] = dst[1] = dst[2] = dst[3] = F;
+    }
+  };
+  // first argmax of s (its maximum M), and the largest value at any other index
+  auto top2 = [&](const int (&s)[VL], int& M, int& M2) -> int {
+    M = wave_max_i(max(max(s[0], s[1]), max(s[2], s[3])));
+    int fk = VL;
+#pragma unroll
+    for (int k = VL - 1; k >= 0; --k) fk = (s[k] == M) ? k : fk;
+    const unsigned long long mask = __ballot(fk < VL);
+    const int L = (int)__builtin_ctzll(mask);
+    const int win = VL * L + __builtin_amdgcn_readlane(fk, L);
+    int o = INT32_MIN;
+#pragma unroll
+    for (int k = 0; k < VL; ++k) o = max(o, (VL * lane + k == win) ? INT32_MIN : s[k]);
+    M2 = wave_max_i(o);
+    return win;
+  };
+  auto fail = [&] {  // 2: the pass ran and did not certify (what the handle's guard counts)
+    if (lane == 0) args.cert[seq] = 2;
+  };
+  int cur, M, M2;
+  {
+    int last[VL];
+    load_row(T - 1, last);
+    cur = top2(last, M, M2);
+    if (!(M > F && (long long)M - M2 >= 2ll * T + 1 + extra(T + 1))) return fail();
+  }
+  int pathreg = 0;
+  if (lane == ((T - 1) & 63)) pathreg = cur;
+  if (((T - 1) & 63) == 0 && lane == 0) path[T - 1] = cur;
+  int ring[PF][VL];
+#pragma unroll
+  for (int u = 0; u < PF; ++u) load_row(T - 2 - u, ring[u]);
+  for (int base = T - 1; base >= 1; base -= PF) {
+#pragma unroll
+    for (int u = 0; u < PF; ++u) {
+      const int t = base - u;
+      if (t >= 1) {
+        const int4 ac = *reinterpret_cast<const int4*>(at + (size_t)cur * NP);
+        const int sv[VL] = {ring[u][0] + ac.x, ring[u][1] + ac.y, ring[u][2] + ac.z, ring[u][3] + ac.w};
+        cur = top2(sv, M, M2);
+        if (!(M > F && (long long)M - M2 >= 2ll * t + 2 + extra(t + 1))) return fail();
+        const int tp = t - 1;
+        if (lane == (tp & 63)) pathreg = cur;
+        if ((tp & 63) == 0 && tp + lane < T) path[tp + lane] = pathreg;  // flush a 64-entry block
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < PF; ++u) load_row(base - PF - 1 - u, ring[u]);
+  }
+  if (lane == 0) args.cert[seq] = 1;
+}
+
+__global__ __launch_bounds__(64) void fix_score_f64(FixScoreArgs r) {
+  const int64_t seq = r.seq_begin + (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (seq >= r.seq_end || r.cert[seq] != 1) return;
+  const int64_t e0 = r.offsets[seq];
+  const int T = (int)(r.offsets[seq + 1] - e0);
+  const int32_t* __restrict__ path = r.path + e0;
+  const int32_t* __restrict__ obs = r.obs + e0;
+  const int N = r.nstates;
+  // the table entry's fixed-point image is above the floor (fix_quantise)
+  auto kept = [](double x) { return __builtin_rint(x * 67108864.0) > (double)kFixFloor; };
+  static_assert(kFixQLog2 == -26, "kept() scales by 2^26");
+  int pp = path[0];
+  const double p0 = r.pi64[pp], b0 = r.et64[(size_t)obs[0] * N + pp];
+  bool ok = kept(p0) && kept(b0);
+  double d = p0 + b0;
+  for (int t = 1; t < T; ++t) {
+    const int p = path[t];
+    const double bv = r.et64[(size_t)obs[t] * N + p];
+    ok = ok && kept(bv);
+    d = (d + r.a64[(size_t)pp * N + p]) + bv;  // (d + a) + b, viterbi.rs:15-17
+    pp = p;
+  }
+  if (ok) {
+    r.score[seq] = d;
+    r.status[seq] = CVK_SEQ_OK;
+  } else {
+    r.cert[seq] = 2;
+  }
+}
+
+bool fix_supported(int np) { return np == 256; }
+
+hipError_t launch_fix_fwd2(int np, const FixFwdArgs& fa, int64_t npairs, hipStream_t stream) {
+  if (npairs <= 0) return hipSuccess;
+  if (np != 256) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((trellis_fwd2_i32<256>), dim3((unsigned)npairs), dim3(1024), 0, stream, fa);
+  return hipGetLastError();
+}
+
+hipError_t launch_fix_bt(int np, const FixBtArgs& ba, hipStream_t stream) {
+  const int64_t n = ba.seq_end - ba.seq_begin;
+  if (n <= 0) return hipSuccess;
+  if (np != 256) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((backtrack_fix_i32<256>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, ba);
+  return hipGetLastError();
+}
+
+hipError_t launch_fix_score(const FixScoreArgs& r, hipStream_t stream) {
+  const int64_t n = r.seq_end - r.seq_begin;
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(fix_score_f64, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, r);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------
 // trellis_wave_f32<NPW, FRC>: small N (NPW = 16, 32, 48 or 64 padded states) -- ONE WAVE per
 // sequence, forward pass and backtrack fused, no workgroup barrier and no cross-wave anything.
 // Forward: lane = 4cq + rg holds rows [R·rg, R·rg + R) (R = NPW/4) of the C = NPW/16 columns

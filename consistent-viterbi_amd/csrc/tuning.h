@@ -57,6 +57,8 @@ struct Tuning {
   int t64_cp_w = 0;            // trellis_cp_f64 waves splitting the columns: 1 never, > 1 always (0: by batch)
   int t64_bt_pf = 0;           // backtrack_f64 rows in flight (0: by NP)
   int t64_lo_every = 8;        // low planes of the delta rows at every K-th row and the last (1: every row; <= 16)
+  int t64_fixed_first = 16777216;  // certified fixed-point first pass of the plain f64 batch decode: the fewest
+                               // elements (sum of lengths) of a call that takes it (0: never)
   // ---- generic and wide kernels (kernels/trellis.hip) ----
   int generic_s = 0;           // sequences per workgroup 1 / 2 / 4 (0: by batch and LDS)
   int generic_split = 0;       // 1: generic_fwd_split (K threads per state)

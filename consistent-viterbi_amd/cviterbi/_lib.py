@@ -46,7 +46,7 @@ EXPORTS = [
     "cv_kbest_batch", "cv_kbest_batch_device",
     "cv_decode_emissions", "cv_decode_emissions_device",
     "cv_posterior_emissions", "cv_posterior_emissions_device",
-    "cv_last_t64_stats",
+    "cv_last_t64_stats", "cv_last_fixed_first_stats",
 ]
 
 
@@ -147,6 +147,7 @@ def lib():
         "cv_decode_superseq_cp": ([P, I64, P, P, P, P], S),
         "cv_last_superseq_stats": ([P, P], S),
         "cv_last_t64_stats": ([P, P, I32], I32),
+        "cv_last_fixed_first_stats": ([P, P, I32], I32),
         "cv_device_memory": ([P, P], S),
         "cv_solver_create": ([ctypes.c_char_p, P, P, P], S),
         "cv_solver_solve": ([P], S),

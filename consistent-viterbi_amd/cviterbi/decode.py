@@ -279,6 +279,21 @@ def last_t64_stats(hmm: HMM) -> dict:
     return {k: int(out[i]) for i, k in enumerate(T64_STATS[:n])}
 
 
+FIXED_FIRST_STATS = ("engaged", "certified", "fallback", "pinned")
+
+
+def last_fixed_first_stats(hmm: HMM) -> dict:
+    """The certified fixed-point first pass of the last decode_batch[_device] call on this handle
+    (cv_last_fixed_first_stats): whether the call took it, the sequences it certified, the
+    sequences the f64 kernels decoded, and whether the handle's guard has pinned it to the f64
+    kernels."""
+    out = (ctypes.c_int64 * len(FIXED_FIRST_STATS))()
+    n = L.lib().cv_last_fixed_first_stats(hmm.handle, out, len(FIXED_FIRST_STATS))
+    if n < 0:
+        L.check(L.CV_EINVAL)
+    return {k: int(out[i]) for i, k in enumerate(FIXED_FIRST_STATS[:n])}
+
+
 def device_memory() -> dict:
     """Device bytes this process's library holds now and at most (cv_device_memory)."""
     cur, peak = ctypes.c_int64(), ctypes.c_int64()

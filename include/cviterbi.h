@@ -208,6 +208,13 @@ CV_API void cv_hmm_destroy(cv_hmm* h);
  *                         the backtrack recomputes the few exact values a near tie on another row
  *                         needs (cv_last_t64_stats).  A handle whose call replayed rows densely more
  *                         than once per 64 sequences (models full of exact ties) runs at 1 from then on
+ *   t64_fixed_first 16777216   cv_decode_batch[_device], f64 row A0 without forced states on
+ *                         log-probability models, 224 < N <= 256: a call of at least this many elements
+ *                         (sum of lengths) first decodes in 32-bit fixed point and keeps every sequence
+ *                         whose path that pass certifies as the f64 decode's own; the others run on the
+ *                         f64 kernels (cv_last_fixed_first_stats).  Such a call waits for its stream
+ *                         once.  A handle that left more than 1 in 8 sequences of a call uncertified
+ *                         stays on the f64 kernels from then on.  0: never (the earlier behaviour)
  *   generic_s 0           generic kernels' sequences per workgroup 1 / 2 / 4 (0: by batch)
  *   generic_split 0, generic_split_k 0   1: K threads per state (generic_fwd_split), its K
  *   generic_wide 1, generic_wide_min 0   0: never wide / > 0: wide from this N
@@ -280,6 +287,13 @@ CV_API cv_status cv_decode_batch_device(cv_hmm* h, int64_t nseq, const int64_t* 
  * replayed densely, so the result is exact all the same, and the handle then stays at 1);
  * 6 the largest need-set; 7 the call's sequences. */
 CV_API int32_t cv_last_t64_stats(const cv_hmm* h, int64_t* out, int32_t n);
+/* Counters of the certified fixed-point first pass (tuning key t64_fixed_first) of the last
+ * cv_decode_batch[_device] call on this handle.  Length-checked like cv_last_t64_stats: writes
+ * min(n, count) words and returns count (4 now), -1 on a bad argument.  Words: 0 whether the call
+ * took the pass (1) or ran on the f64 kernels alone (0); 1 sequences whose path the pass
+ * certified; 2 sequences decoded by the f64 kernels (1 + 2 = the call's sequences when word 0
+ * is 1); 3 whether the handle's guard has pinned it to the f64 kernels. */
+CV_API int32_t cv_last_fixed_first_stats(const cv_hmm* h, int64_t* out, int32_t n);
 /* Device timings of the last decode call on this handle (synchronizes its events). */
 CV_API cv_status cv_last_timing(cv_hmm* h, cv_timing* out);
 /* Device timings summed over EVERY decode call on this handle from cv_timing_begin to
