@@ -1858,6 +1858,10 @@ CV_API cv_status cv_hmm_release_workspaces(cv_hmm* h) {
   // every stream the workspaces were used on has drained before the memory goes
   for (hipStream_t s : {h->stream, h->bt_stream, h->side.stream, h->side.hi, h->copy_stream, h->chain_stream})
     if (s) HIP_TRY(hipStreamSynchronize(s));
+  // ... and so has the caller's stream of the last *_device call, up to that call's end (ws_done
+  // follows its last kernel): the workspaces are idle by the events, not by hipFree's own wait
+  if (h->ws_rec) HIP_TRY(hipEventSynchronize(h->ws_done));
+  if (h->side.ws_rec) HIP_TRY(hipEventSynchronize(h->side.ws_done));
   for (DevBuf* b : {&h->ws_main, &h->ws_last, &h->ws_order, &h->side.main, &h->side.last, &h->side.order,
                     &h->side.idx, &h->side.obs2, &h->side.path2, &h->side.res2, &h->st_off, &h->st_obs, &h->st_path,
                     &h->st_score, &h->st_status, &h->st_forced, &h->cs_ranges, &h->cs_delta, &h->cs_g, &h->cs_mu,
@@ -1867,7 +1871,8 @@ CV_API cv_status cv_hmm_release_workspaces(cv_hmm* h) {
                     &h->chainb.off, &h->chainb.obs, &h->chainb.path, &h->chainb.res, &h->chainb.cert, &h->chainb.ebin,
                     &h->chainb.q, &h->chainb.ends, &h->chainb.gid, &h->chainb.gpath, &h->chainb.first,
                     &h->chainb.rpsi, &h->chainb.rows, &h->chainb.small, &h->chainb.rpath, &h->chainb.soff,
-                    &h->chainb.sobs, &h->chainb.spath, &h->chainb.sres, &h->chainb.sinit, &h->chainb.slast, &h->ps_rows,
+                    &h->chainb.sobs, &h->chainb.spath, &h->chainb.sres, &h->chainb.sinit, &h->chainb.slast,
+                    &h->chainb.spsi, &h->ps_rows,
                     &h->ps_order, &h->ps_kshift, &h->st_gamma, &h->kb_bp, &h->kb_last, &h->kb_order, &h->kb_end, &h->st_count,
                     &h->st_emis, &h->fx_cert, &h->fx_idx, &h->fx_obs2, &h->fx_path2, &h->fx_score2, &h->fx_status2})
     b->release();

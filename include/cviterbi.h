@@ -233,7 +233,9 @@ CV_API void cv_hmm_destroy(cv_hmm* h);
  * so repeated calls do not reallocate: e.g. ~1 GB of chain buffers (observations, paths, the
  * speculative batches' psi rows) and 18 MiB of pinned staging plus the 34-69 GB delta workspace
  * after a config-4-sized cv_decode_superseq_cp / cv_decode_batch.  The model tables
- * stay; the next call allocates what it needs again.  Waits for the handle's streams. */
+ * stay; the next call allocates what it needs again, and cv_device_memory is back at what the
+ * tables alone take.  Waits for the handle's streams and, on the caller's stream of the last
+ * *_device call, for that call's end: releasing while such a call is in flight is safe. */
 CV_API cv_status cv_hmm_release_workspaces(cv_hmm* h);
 CV_API cv_status cv_hmm_set_tuning(cv_hmm* h, const char* key, int64_t value);
 CV_API cv_status cv_hmm_get_tuning(const cv_hmm* h, const char* key, int64_t* value);
