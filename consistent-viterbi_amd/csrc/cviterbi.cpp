@@ -40,6 +40,7 @@
 #include "kernels/emis.h"
 #include "kernels/kbest.h"
 #include "kernels/posterior.h"
+#include "kernels/sample.h"
 #include "kernels/trellis.h"
 #include "kernels/trellis64.h"
 #include "tuning.h"
@@ -285,6 +286,7 @@ struct cv_hmm {
   // host API's gamma staging
   DevBuf ps_rows, ps_order, st_gamma;
   DevBuf ps_kshift;  // cv_posterior_emissions*: each sequence's sum of row-scale exponents (int64)
+  PinnedHost sm_pin;  // cv_sample_batch: the log-likelihoods and score planes on their way to the caller
   OrderStage ps_pin;
   // K-best workspace: the u16 back-pointers of one chunk, each sequence's last lists, the
   // longest-first order, the ranks' end points, and the host API's count staging
@@ -1455,6 +1457,15 @@ cv_status posterior_opts_ok(const cv_hmm* h, const cv_opts& o) {
   return CV_OK;
 }
 
+// cv_sample_batch*: what the sampler puts in place of the backward pass of a chunk (sample_device)
+struct SampleReq {
+  int32_t draws;
+  uint64_t seed;
+  int64_t seq_base;
+  int32_t* path;  // device, [draws][offsets[nseq]]
+  double* score;  // device, [draws][nseq], nullable
+};
+
 // Core of cv_posterior_batch*: all pointers are device pointers except offsets_host.  Chunks of
 // whole sequences (original order) whose forward rows fit the workspace cap run forward then
 // backward on `stream`; scoring mode (no path, no gamma) is one forward launch with no rows.
@@ -1463,11 +1474,16 @@ cv_status posterior_opts_ok(const cv_hmm* h, const cv_opts& o) {
 // rows are staged in probability space behind its forward rows (emis_prepare_lin_f64: 8 NP + 4
 // bytes per element more, under the same cap -- so the scoring mode is chunked too) and stay
 // there until its backward pass has run; the sequences' row-scale exponents go to ps_kshift.
+// smp (cv_sample_batch*): the rows are stored and each chunk's backward pass is replaced by the
+// sampler's walk and the scores of its paths; everything else -- planning, order, events -- is
+// this function's, so a sampling call chunks and times exactly like a posterior call.
 cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, const int64_t* offsets_dev,
                            const int32_t* obs_dev, const cv_opts& o, double* loglik_dev, int32_t* path_dev,
-                           double* gamma_dev, uint8_t* status_dev, hipStream_t stream, const EmisSrc* emis = nullptr) {
+                           double* gamma_dev, uint8_t* status_dev, hipStream_t stream, const EmisSrc* emis = nullptr,
+                           const SampleReq* smp = nullptr) {
   cv_status st = posterior_opts_ok(h, o);
   if (st != CV_OK) return st;
+  if (smp && smp->score && (st = ensure_f64_tables(h)) != CV_OK) return st;
   const bool generic = o.kernel == CV_KERNEL_GENERIC || h->N > cvp::kPostMmStates;
   std::vector<int64_t> off_copy;
   if ((st = host_offsets(nseq, offsets_host, offsets_dev, off_copy, stream)) != CV_OK) return st;
@@ -1480,7 +1496,7 @@ cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
   if (nseq == 0) return CV_OK;
   if (h->ws_rec) HIP_TRY(hipStreamWaitEvent(stream, h->ws_done, 0));
 
-  const bool store = path_dev || gamma_dev;
+  const bool store = path_dev || gamma_dev || smp;
   const uint64_t row_bytes = (uint64_t)np * 8;
   const uint64_t per_elem = (store ? row_bytes : 0) + (emis ? row_bytes + 4 : 0);
   std::vector<cvplan::Chunk> chunks;
@@ -1577,7 +1593,45 @@ cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
     if (err != hipSuccess) return set_err(CV_EDEVICE, "posterior forward launch failed: %s", hipGetErrorString(err));
     HIP_TRY(hipEventRecord(f1, stream));
     HIP_TRY(hipEventRecord(b0, stream));
-    if (store) {
+    if (smp) {
+      cvs::SampleArgs sg{};
+      sg.at = g.at;
+      sg.rows = g.rows;
+      sg.offsets = offsets_dev;
+      sg.order = order_dev;
+      sg.seq_begin = c.first;
+      sg.seq_end = c.second;
+      sg.elem_base = g.elem_base;
+      sg.nstates = h->N;
+      sg.np = np;
+      sg.status = status_dev;
+      sg.path = smp->path;
+      sg.plane = offsets_host[nseq];
+      sg.draws = smp->draws;
+      sg.seed = smp->seed;
+      sg.seq_base = smp->seq_base;
+      err = cvs::launch_sample(sg, generic, stream);
+      if (err == hipSuccess && smp->score) {
+        cvs::SampleScoreArgs ss{};
+        ss.path = smp->path;
+        ss.plane = sg.plane;
+        ss.draws = smp->draws;
+        ss.obs = obs_dev;
+        ss.offsets = offsets_dev;
+        ss.order = order_dev;
+        ss.seq_begin = c.first;
+        ss.seq_end = c.second;
+        ss.nseq = nseq;
+        ss.nstates = h->N;
+        ss.pi64 = h->d_pi64.as<double>();
+        ss.a64 = h->d_a64.as<double>();
+        ss.et64 = h->d_et64.as<double>();
+        ss.status = status_dev;
+        ss.score = smp->score;
+        err = cvs::launch_sample_score(ss, stream);
+      }
+      if (err != hipSuccess) return set_err(CV_EDEVICE, "sampling launch failed: %s", hipGetErrorString(err));
+    } else if (store) {
       err = cvp::launch_post_bwd(g, generic, stream);
       if (err != hipSuccess) return set_err(CV_EDEVICE, "posterior backward launch failed: %s", hipGetErrorString(err));
     }
@@ -1585,6 +1639,24 @@ cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
     h->last_launches = (int64_t)ci + 1;
   }
   return end_call(h, false, nev, stream);
+}
+
+// Core of cv_sample_batch*: forward filtering, backward sampling.  posterior_device's plan with the
+// sampler in place of the backward pass; all pointers are device pointers except offsets_host.
+cv_status sample_draws_ok(int32_t draws) {
+  if (draws < 1 || draws > cvs::kSampleMaxDraws)
+    return set_err(CV_EINVAL, "draws = %d outside [1, %d]", draws, cvs::kSampleMaxDraws);
+  return CV_OK;
+}
+cv_status sample_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, const int64_t* offsets_dev,
+                        const int32_t* obs_dev, int32_t draws, uint64_t seed, int64_t seq_base, const cv_opts& o,
+                        int32_t* path_dev, double* score_dev, double* loglik_dev, uint8_t* status_dev,
+                        hipStream_t stream) {
+  cv_status st = sample_draws_ok(draws);
+  if (st != CV_OK) return st;
+  const SampleReq smp{draws, seed, seq_base, path_dev, score_dev};
+  return posterior_device(h, nseq, offsets_host, offsets_dev, obs_dev, o, loglik_dev, nullptr, nullptr, status_dev, stream,
+                          nullptr, &smp);
 }
 
 // ---- K-best (list) Viterbi: cv_kbest_batch* ---------------------------------------------------
@@ -1877,6 +1949,7 @@ CV_API cv_status cv_hmm_release_workspaces(cv_hmm* h) {
                     &h->st_emis, &h->fx_cert, &h->fx_idx, &h->fx_obs2, &h->fx_path2, &h->fx_score2, &h->fx_status2})
     b->release();
   h->fx_cert_pin.release();
+  h->sm_pin.release();
   h->ws_rec = false;
   h->side.ws_rec = false;
   h->chain_pin.release();
@@ -2282,6 +2355,70 @@ CV_API cv_status cv_posterior_batch(cv_hmm* h, int64_t nseq, const int64_t* offs
   for (int64_t s = 0; s < nseq; ++s)
     if (status_out[s] == CV_SEQ_INFEASIBLE)
       return set_err(CV_EINFEASIBLE, "sequence %lld has likelihood 0", (long long)s);
+  return CV_OK;
+}
+
+// ---- posterior path sampling: cv_sample_batch* -------------------------------------------------
+CV_API cv_status cv_sample_batch_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
+                                        const int64_t* offsets_dev, const int32_t* obs_dev, int32_t draws,
+                                        uint64_t seed, int64_t seq_base, const cv_opts* opts, int32_t* path_dev,
+                                        double* score_dev, double* loglik_dev, uint8_t* status_dev) {
+  if (!h) return set_err(CV_EINVAL, "null handle");
+  if (nseq < 0) return set_err(CV_EINVAL, "nseq < 0");
+  cv_status st = sample_draws_ok(draws);
+  if (st != CV_OK) return st;
+  if (nseq > 0 && (!offsets_dev || !obs_dev || !path_dev || !status_dev)) return set_err(CV_EINVAL, "null device buffer");
+  CV_LOCK(h);
+  if ((st = set_device(h)) != CV_OK) return st;
+  const cv_opts o = opts ? *opts : default_opts();
+  hipStream_t stream = o.stream ? (hipStream_t)o.stream : h->stream;
+  double* ll = loglik_dev;
+  if (!ll && nseq > 0) {  // the forward pass always writes the log-likelihoods: to the staging when nobody asks
+    if ((st = h->st_score.ensure((size_t)nseq * 8)) != CV_OK) return st;
+    ll = h->st_score.as<double>();
+  }
+  return sample_device(h, nseq, offsets_host, offsets_dev, obs_dev, draws, seed, seq_base, o, path_dev, score_dev, ll,
+                       status_dev, stream);
+}
+
+CV_API cv_status cv_sample_batch(cv_hmm* h, int64_t nseq, const int64_t* offsets, const int32_t* obs, int32_t draws,
+                                 uint64_t seed, int64_t seq_base, const cv_opts* opts, int32_t* path_out,
+                                 double* score_out, double* loglik_out, uint8_t* status_out) {
+  if (!h) return set_err(CV_EINVAL, "null handle");
+  cv_status st = sample_draws_ok(draws);
+  if (st != CV_OK) return st;
+  if (nseq < 0 || (nseq > 0 && (!offsets || !obs || !path_out || !status_out))) return set_err(CV_EINVAL, "null argument");
+  CV_LOCK(h);
+  if ((st = set_device(h)) != CV_OK) return st;
+  cv_opts o = opts ? *opts : default_opts();
+  if (nseq == 0) return CV_OK;
+  const size_t R = (size_t)draws, B = (size_t)nseq;
+  // the observations are range-checked on the device (CV_SEQ_BADOBS), as in the _device variant
+  HostBatch hb{h, nseq, offsets, obs, o.stream ? (hipStream_t)o.stream : h->stream};
+  // st_score: [nseq] log-likelihoods, then the [R][nseq] score planes
+  if ((st = hb.stage(o, R, R + 1)) != CV_OK) return st;
+  double* const ll_dev = h->st_score.as<double>();
+  double* const sc_dev = score_out ? ll_dev + B : nullptr;
+  st = sample_device(h, nseq, offsets, h->st_off.as<int64_t>(), h->st_obs.as<int32_t>(), draws, seed, seq_base, o,
+                     h->st_path.as<int32_t>(), sc_dev, ll_dev, h->st_status.as<uint8_t>(), hb.stream);
+  if (st != CV_OK) return hb.fail(st);
+  for (size_t r = 0; r < R; ++r)  // plane r of the staging and of path_out: offsets[nseq] elements each
+    hb.fetch_elems(path_out, h->st_path, 1, r);
+  // the scores come back through pinned staging: an empty sequence's slots of score_out stay untouched
+  const size_t nsc = (score_out ? R * B : 0) + B;
+  if (!h->sm_pin.ensure(nsc * 8)) return hb.fail(set_err(CV_ENOMEM, "pinned staging of %zu scores failed", nsc));
+  double* const pin = h->sm_pin.as<double>();
+  if (hb.err == hipSuccess) hb.err = hipMemcpyAsync(pin, ll_dev, nsc * 8, hipMemcpyDeviceToHost, hb.stream);
+  hb.fetch_seqs(status_out, h->st_status);
+  if ((st = hb.finish()) != CV_OK) return st;
+  if (loglik_out) std::memcpy(loglik_out, pin, B * 8);
+  int64_t infeasible = -1;
+  for (int64_t s = 0; s < nseq; ++s) {
+    if (status_out[s] == CV_SEQ_INFEASIBLE && infeasible < 0) infeasible = s;
+    if (score_out && status_out[s] != CV_SEQ_EMPTY)
+      for (size_t r = 0; r < R; ++r) score_out[r * B + (size_t)s] = pin[B + r * B + (size_t)s];
+  }
+  if (infeasible >= 0) return set_err(CV_EINFEASIBLE, "sequence %lld has likelihood 0", (long long)infeasible);
   return CV_OK;
 }
 

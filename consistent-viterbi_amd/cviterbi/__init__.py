@@ -13,5 +13,6 @@ from .emissions import posterior_emissions, posterior_emissions_device, score_em
 from .fit import fit_mle, fit_train  # noqa: F401
 from .kbest import kbest_batch, kbest_batch_device  # noqa: F401
 from .posterior import posterior_batch, posterior_batch_device, score_batch  # noqa: F401
+from .sample import sample_batch, sample_batch_device, uniform  # noqa: F401
 from .solver import (Constraints, GpuSolver, Solver, SuperSequence, load_sequences, load_tags,  # noqa: F401
                      write_output)

@@ -46,6 +46,7 @@ EXPORTS = [
     "cv_kbest_batch", "cv_kbest_batch_device",
     "cv_decode_emissions", "cv_decode_emissions_device",
     "cv_posterior_emissions", "cv_posterior_emissions_device",
+    "cv_sample_batch", "cv_sample_batch_device",
     "cv_last_t64_stats", "cv_last_fixed_first_stats",
 ]
 
@@ -126,6 +127,8 @@ def lib():
         "cv_decode_batch_device": ([P, I64, P, P, P, P, P, P, P], S),
         "cv_posterior_batch": ([P, I64, P, P, P, P, P, P, P], S),
         "cv_posterior_batch_device": ([P, I64, P, P, P, P, P, P, P, P], S),
+        "cv_sample_batch": ([P, I64, P, P, I32, ctypes.c_uint64, I64, P, P, P, P, P], S),
+        "cv_sample_batch_device": ([P, I64, P, P, P, I32, ctypes.c_uint64, I64, P, P, P, P, P], S),
         "cv_kbest_batch": ([P, I64, P, P, I32, P, P, P, P, P], S),
         "cv_kbest_batch_device": ([P, I64, P, P, P, I32, P, P, P, P, P], S),
         "cv_decode_emissions": ([P, I64, P, P, I64, P, P, P, P], S),

@@ -228,7 +228,7 @@ CV_API void cv_hmm_destroy(cv_hmm* h);
  *                         per-sequence E-step kernels / the xi GEMM path at every N
  * Unknown keys and values outside int32 are CV_EINVAL.  cv_tuning_key(i) lists the keys
  * (NULL past the last). */
-/* Frees the handle's decode workspaces (delta rows, the posterior path's forward rows, the K-best back-pointers and last lists, the
+/* Frees the handle's decode workspaces (delta rows, the posterior and sampling paths' forward rows, the K-best back-pointers and last lists, the
  * constrained decode's and the parallel chain's per-call buffers, pinned staging), which are otherwise kept grow-only between calls
  * so repeated calls do not reallocate: e.g. ~1 GB of chain buffers (observations, paths, the
  * speculative batches' psi rows) and 18 MiB of pinned staging plus the 34-69 GB delta workspace
@@ -459,6 +459,65 @@ CV_API cv_status cv_posterior_batch_device(cv_hmm* h, int64_t nseq, const int64_
                                            const int64_t* offsets_dev, const int32_t* obs_dev, const cv_opts* opts,
                                            double* loglik_dev, int32_t* path_dev, double* gamma_dev,
                                            uint8_t* status_dev);
+
+/* ---- evaluation: posterior path sampling (forward filtering, backward sampling) ------------
+ * `draws` = R whole paths per sequence from P(path | observations, tags), the model read exactly
+ * as cv_posterior_batch reads it (VITERBI association, p = 10^x, a forced element admits one
+ * state).  The forward pass is cv_posterior_batch's (the scaled rows alpha^_t in the handle's
+ * workspace); draw r of sequence s then walks back from the last element:
+ *   t = T-1: weights w_i = alpha^_t[i];
+ *   t < T-1: w_i = alpha^_t[i] * A[i][j] (one f64 product), j the state already drawn for t+1 --
+ *     the emission and the mask of t+1 are constant in i and drop out;
+ *   pick: with W = sum_i w_i and the inclusive prefix sums c_i in state order, the smallest i with
+ *     w_i > 0 and c_i > u W; if rounding leaves none, the largest i with w_i > 0.  The association
+ *     order of the sums is the kernel's own and fixed, so results repeat bit for bit.  A state
+ *     with w_i = 0 is never picked, whatever the rounding: every returned path has a finite
+ *     joint score (unlike cv_posterior_batch's path, the per-element argmax of gamma, which can
+ *     cross a zero transition).
+ * u = u(seed, S, r, t), S = seq_base + s, t the position in the sequence, is a counter-based
+ * uniform on [0, 1), all arithmetic mod 2^64, G = 0x9E3779B97F4A7C15:
+ *   mix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31
+ *   k = mix(seed + G); k = mix(k ^ S); k = mix(k + G (r + 1)); z = mix(k ^ (t * 0xD1B54A32D192ED03))
+ *   u = (z >> 11) * 2^-53
+ * e.g. u(0, 0, 0, 0) = 0x1.da202e598192dp-1, u(1, 2, 3, 4) = 0x1.cfd7060f11400p-6.  A draw depends
+ * on (seed, S, r) and the sequence alone -- not on the batch around it, the chunking, R or the
+ * variant: the first R' planes of an R-draw call are the R'-draw call; sequence s of a batch is
+ * the same sequence sampled alone with seq_base = s; a multi-GPU caller shards with seq_base.
+ * CV_KERNEL_AUTO and CV_KERNEL_GENERIC may pick differently (their forward rows differ in the
+ * last bits); both meet the accuracy contract:
+ *   with F the exact conditional CDF given the state drawn at t+1, the picked i satisfies
+ *   F_(i-1) - eps <= u <= F_i + eps, eps(T, N) = 4 (T + 1) (N + 8) 2^-53
+ * (forward rows within 2 T (N + 8) u relative, N + 2 roundings in each of the numerator and the
+ * denominator; DESIGN.md, Posterior sampling).
+ * Outputs, with L = offsets[nseq]: path_out is draw-major, plane r (path_out + r * L) a whole path
+ * array in cv_decode_batch's layout; score_out[r * nseq + s] (nullable; draw-major too, so every
+ * plane is a cv_decode_batch-shaped result) is the reference's f64 fold along the sampled path,
+ *   d = pi[s_0] + b[s_0, o_0], then d = (d + a[s_t-1, s_t]) + b[s_t, o_t],
+ * bit for bit what cv_kbest_batch reports for the same path; loglik_out[s] (nullable) as
+ * cv_posterior_batch.  1 <= draws <= 64 (else CV_EINVAL).
+ * status_out as cv_posterior_batch: CV_SEQ_BADOBS (paths -1, scores NaN, loglik NaN);
+ * CV_SEQ_INFEASIBLE (paths -1, scores -inf, loglik -inf; the host variant returns
+ * CV_EINFEASIBLE after writing every output); CV_SEQ_EMPTY (loglik 0; no path element exists and
+ * the sequence's score_out slots are not written).  No sequence disturbs another.
+ * opts exactly as cv_posterior_batch: dtype CV_DTYPE_F64, assoc CV_ASSOC_VITERBI, kernel
+ * CV_KERNEL_AUTO (N <= 256: one wave per sequence and group of up to 8 draws) or CV_KERNEL_GENERIC
+ * (one workgroup per sequence and draw; every N > 256), forced, stream, workspace_bytes (the
+ * rows: NP * 8 bytes per element, chunks of whole sequences).  N <= 4096.
+ * cv_last_timing: fwd_ms the forward pass, bt_ms sampling plus scoring, the rest as for
+ * cv_posterior_batch.  cv_hmm_release_workspaces frees the rows and the staging.
+ * Host pointers; synchronous. */
+CV_API cv_status cv_sample_batch(cv_hmm* h, int64_t nseq, const int64_t* offsets, const int32_t* obs,
+                                 int32_t draws, uint64_t seed, int64_t seq_base, const cv_opts* opts,
+                                 int32_t* path_out /*[draws][L]*/, double* score_out /*[draws][nseq], nullable*/,
+                                 double* loglik_out /*[nseq], nullable*/, uint8_t* status_out /*[nseq]*/);
+/* The same on device-resident buffers, with cv_posterior_batch_device's contract: enqueued on
+ * opts->stream (or the handle's stream), returns after enqueueing (so it reports CV_OK where
+ * the host variant reports CV_EINFEASIBLE: read status_dev); offsets_host (nullable) is a host
+ * copy of the offsets; opts->forced is a device pointer. */
+CV_API cv_status cv_sample_batch_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
+                                        const int64_t* offsets_dev, const int32_t* obs_dev, int32_t draws,
+                                        uint64_t seed, int64_t seq_base, const cv_opts* opts, int32_t* path_dev,
+                                        double* score_dev, double* loglik_dev, uint8_t* status_dev);
 
 /* ---- K-best (list) Viterbi decoding, exact f64 --------------------------------------------
  * The k best paths of every sequence under the row-A0 (VITERBI) association in f64, with their
