@@ -1329,7 +1329,8 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
         fa.cp_last = rq.cp_last;
         err = cvk::launch_t64_cp_fwd(h->np64, spw, fa, n, stream);
       } else {
-        fa.nstates = h->N;  // the N <= 48 one-wave kernel
+        fa.nstates = h->N;  // the N <= 48 one-wave kernel, the few-sequence layout
+        if (!side_ws && cvk::t64_few_launch(h->np64, fa, n)) h->last_mt = 0;
         err = cvk::launch_t64_fwd(h->np64, spw, fa, n, stream);
       }
     } else if (o.dtype == CV_DTYPE_F64) {
@@ -2109,10 +2110,22 @@ static cv_status fixed_first_decode(cv_hmm* h, int64_t nseq, const int64_t* offs
   // chunk equal-length neighbours of the longest-first order are paired, the leftovers fall back
   const uint64_t per_elem = (uint64_t)np * 4;
   const uint64_t cap = o.workspace_bytes ? o.workspace_bytes : default_workspace_cap(h->ws_main.bytes, kDefaultWorkspaceT64);
+  // Tuning key t64_fixed_chunks (bit-identical): k > 0, the default: the chunks are pipelined over
+  // two streams as the f32 trellis's are -- at least min(k, nseq / 2048) of them out of a
+  // double-buffered workspace, chunk k's certificate backtrack and score on bt_stream beside the
+  // forward of chunk k + 1; 0: the chunks back to back on the caller's stream, one under the cap
+  const int fchunks = h->tuning.t64_fixed_chunks;
+  const bool one_stream = fchunks <= 0;
   std::vector<cvplan::Chunk> chunks;
-  cvplan::split_pipelined(offsets_host, nseq, {per_elem, cap, true, 8, 2 * (int64_t)std::max(h->cus, 1)}, chunks);
+  cvplan::split_pipelined(offsets_host, nseq,
+                          {per_elem, cap, one_stream, one_stream ? 8u : (uint64_t)std::min(fchunks, 64),
+                           2 * (int64_t)std::max(h->cus, 1)},
+                          chunks);
   const cvplan::Shares largest = cvplan::measure(offsets_host, chunks);
-  if ((st = h->ws_main.ensure(std::max<uint64_t>(largest.max_elems, 1) * per_elem)) != CV_OK) return st;
+  const bool serial = one_stream || chunks.size() == 1;  // a single chunk has no forward to run beside
+  const int nbuf = serial ? 1 : 2;
+  const size_t buf_bytes = ((std::max<uint64_t>(largest.max_elems, 1) * per_elem + 255) / 256) * 256;
+  if ((st = h->ws_main.ensure(buf_bytes * nbuf)) != CV_OK) return st;
   if ((st = h->fx_cert.ensure((size_t)nseq)) != CV_OK) return st;
   if (!h->fx_cert_pin.ensure((size_t)nseq)) return set_err(CV_ENOMEM, "pinned certificate copy failed");
   if (h->ws_rec) HIP_TRY(hipStreamWaitEvent(stream, h->ws_done, 0));
@@ -2140,11 +2153,25 @@ static cv_status fixed_first_decode(cv_hmm* h, int64_t nseq, const int64_t* offs
   const size_t nev = 4 * chunks.size();
   size_t eb;
   if ((st = reserve_events(h, false, nev, &eb)) != CV_OK) return st;
+  hipStream_t bts = serial ? stream : h->bt_stream;
+  // work enqueued on the second stream is joined by the caller's stream below; if the call fails
+  // before that, it is waited for here, so no kernel of a failed call is left running on a stream
+  // the caller does not see
+  struct BtJoin {
+    hipStream_t s;
+    bool pending = false;
+    ~BtJoin() {
+      if (pending) (void)hipStreamSynchronize(s);
+    }
+  } bt_join{h->bt_stream};
   for (size_t ci = 0; ci < chunks.size(); ++ci) {
     const cvplan::Chunk c = chunks[ci];
     const int64_t n = c.second - c.first;
     const int64_t np2 = varlen ? npair[ci] : n / 2;
-    HIP_TRY(hipEventRecord(h->ev[eb + 4 * ci], stream));
+    hipEvent_t* const e4 = &h->ev[eb + 4 * ci];
+    hipEvent_t f0 = e4[0], f1 = e4[1], b0 = e4[2], b1 = e4[3];
+    if (!serial && ci >= 2) HIP_TRY(hipStreamWaitEvent(stream, h->ev[eb + 4 * (ci - 2) + 3], 0));  // buffer reuse
+    HIP_TRY(hipEventRecord(f0, stream));
     cvk::FixFwdArgs fa{};
     fa.a_img = h->fx_aimg.as<int32_t>();
     fa.pi = h->fx_pi.as<int32_t>();
@@ -2153,14 +2180,21 @@ static cv_status fixed_first_decode(cv_hmm* h, int64_t nseq, const int64_t* offs
     fa.obs = obs_dev;
     fa.order = order_dev;
     fa.seq_begin = c.first;
-    fa.rows = h->ws_main.as<int32_t>();
+    fa.rows = reinterpret_cast<int32_t*>(h->ws_main.as<unsigned char>() + (nbuf == 2 ? ci % 2 : 0) * buf_bytes);
     fa.row_elem_base = offsets_host[c.first];
     fa.cert = h->fx_cert.as<uint8_t>();
     fa.nobs = (int)h->V;
     hipError_t err = cvk::launch_fix_fwd2(np, fa, np2, stream);
     if (err != hipSuccess) return set_err(CV_EDEVICE, "fixed-point forward launch failed: %s", hipGetErrorString(err));
-    HIP_TRY(hipEventRecord(h->ev[eb + 4 * ci + 1], stream));
-    HIP_TRY(hipEventRecord(h->ev[eb + 4 * ci + 2], stream));
+    HIP_TRY(hipEventRecord(f1, stream));
+    if (!serial) {
+      HIP_TRY(hipStreamWaitEvent(bts, f1, 0));
+      bt_join.pending = true;
+    }
+    HIP_TRY(hipEventRecord(b0, bts));
+    // beside the next chunk's forward: one backtrack / score workgroup per CU (launch_fix_bt); the
+    // last chunk's have the device to themselves
+    const int reserve = (serial || ci + 1 == chunks.size()) ? 0 : 100 * 1024;
     cvk::FixBtArgs ba{};
     ba.rows = fa.rows;
     ba.row_elem_base = fa.row_elem_base;
@@ -2172,7 +2206,7 @@ static cv_status fixed_first_decode(cv_hmm* h, int64_t nseq, const int64_t* offs
     ba.gain = h->fx_gain;
     ba.path = path_dev;
     ba.cert = fa.cert;
-    err = cvk::launch_fix_bt(np, ba, stream);
+    err = cvk::launch_fix_bt(np, ba, bts, reserve);
     if (err == hipSuccess) {
       cvk::FixScoreArgs ra{};
       ra.path = path_dev;
@@ -2187,10 +2221,15 @@ static cv_status fixed_first_decode(cv_hmm* h, int64_t nseq, const int64_t* offs
       ra.cert = fa.cert;
       ra.score = score_dev;
       ra.status = status_dev;
-      err = cvk::launch_fix_score(ra, stream);
+      err = cvk::launch_fix_score(ra, bts, reserve);
     }
     if (err != hipSuccess) return set_err(CV_EDEVICE, "fixed-point backtrack launch failed: %s", hipGetErrorString(err));
-    HIP_TRY(hipEventRecord(h->ev[eb + 4 * ci + 3], stream));
+    HIP_TRY(hipEventRecord(b1, bts));
+  }
+  // the caller's stream sees every chunk's paths, scores and certificates
+  if (!serial) {
+    HIP_TRY(hipStreamWaitEvent(stream, h->ev[eb + 4 * (chunks.size() - 1) + 3], 0));
+    bt_join.pending = false;
   }
   if ((st = end_call(h, false, nev, stream)) != CV_OK) return st;
   HIP_TRY(hipMemcpyAsync(h->fx_cert_pin.p, h->fx_cert.p, (size_t)nseq, hipMemcpyDeviceToHost, stream));

@@ -120,8 +120,9 @@ struct FixScoreArgs {
 };
 bool fix_supported(int np);
 hipError_t launch_fix_fwd2(int np, const FixFwdArgs& fa, int64_t npairs, hipStream_t stream);
-hipError_t launch_fix_bt(int np, const FixBtArgs& ba, hipStream_t stream);
-hipError_t launch_fix_score(const FixScoreArgs& r, hipStream_t stream);
+// lds_reserve as launch_trellis_bt: beside the next chunk's integer forward, one workgroup per CU
+hipError_t launch_fix_bt(int np, const FixBtArgs& ba, hipStream_t stream, int lds_reserve = 0);
+hipError_t launch_fix_score(const FixScoreArgs& r, hipStream_t stream, int lds_reserve = 0);
 
 template <typename REAL>
 struct GenericFwdArgs {

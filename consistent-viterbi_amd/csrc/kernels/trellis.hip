@@ -1229,18 +1229,29 @@ hipError_t launch_fix_fwd2(int np, const FixFwdArgs& fa, int64_t npairs, hipStre
   return hipGetLastError();
 }
 
-hipError_t launch_fix_bt(int np, const FixBtArgs& ba, hipStream_t stream) {
+// lds_reserve > 0 (the pipelined pass, every chunk but the last): dynamic LDS the workgroup reserves
+// and does not use, so that at most one of them shares a CU with the integer forward of the next
+// chunk (2 x 100 KiB > 160 KiB) and a forward workgroup always finds its registers free: 4 forward
+// waves x 112 VGPRs per SIMD leave 64, one backtrack (60) or score (22) wave (see trellis_bt_np)
+hipError_t launch_fix_bt(int np, const FixBtArgs& ba, hipStream_t stream, int lds_reserve) {
   const int64_t n = ba.seq_end - ba.seq_begin;
   if (n <= 0) return hipSuccess;
   if (np != 256) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((backtrack_fix_i32<256>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, ba);
+  if (lds_reserve > 0)  // per device, so set on every such launch (a few per call)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&backtrack_fix_i32<256>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  hipLaunchKernelGGL((backtrack_fix_i32<256>), dim3((unsigned)((n + 3) / 4)), dim3(256), (size_t)lds_reserve, stream,
+                     ba);
   return hipGetLastError();
 }
 
-hipError_t launch_fix_score(const FixScoreArgs& r, hipStream_t stream) {
+hipError_t launch_fix_score(const FixScoreArgs& r, hipStream_t stream, int lds_reserve) {
   const int64_t n = r.seq_end - r.seq_begin;
   if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(fix_score_f64, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, r);
+  if (lds_reserve > 0)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fix_score_f64), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              160 * 1024);
+  hipLaunchKernelGGL(fix_score_f64, dim3((unsigned)((n + 63) / 64)), dim3(64), (size_t)lds_reserve, stream, r);
   return hipGetLastError();
 }
 

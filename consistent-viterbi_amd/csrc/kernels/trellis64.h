@@ -263,6 +263,9 @@ int t64_support_states(int n);
 // sequences per forward wave (2, 4 or 8) for a launch of nseq sequences on `cus` CUs
 int t64_seqs_per_wave(int64_t nseq, int cus, int np = 0);
 hipError_t launch_t64_fwd(int np, int s, const T64FwdArgs& fa, int64_t nseq, hipStream_t stream);
+// launch_t64_fwd runs this launch on the few-sequence layout (trellis_few_f64: NP = 256, plain row
+// A0, 192 < N; tuning key t64_few), one 16-wave workgroup per two sequences
+bool t64_few_launch(int np, const T64FwdArgs& fa, int64_t nseq);
 // CP association (cp.rs:70-79): psi and the CP value d[psi] + (a[psi,j] + b[j,o]) in the forward
 // the CP forward's layout for a batch: waves per workgroup splitting the columns, then
 // sequences per workgroup for a requested s

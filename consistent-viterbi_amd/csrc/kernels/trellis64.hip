@@ -2451,6 +2451,129 @@ hipError_t fwd_512(const T64FwdArgs& fa, int64_t nseq, hipStream_t stream) {
   return hipGetLastError();
 }
 
+// trellis_few_f64: NP = 256, the plain row-A0 recurrence (no EXT, DPSolver association or
+// zero_init) for launches too small to fill the chip with the pair-of-waves layouts: one
+// 16-wave workgroup -- a whole CU -- per TWO sequences.  The waves split the columns (16 each);
+// inside a wave lane = (column c = lane & 15, row group rg = lane >> 4) takes rows 4k + rg, so
+// one load instruction covers four 128-byte segments of A and every A row is fetched from L2
+// once per workgroup-step for both sequences (512 KiB per step: the layout's bound is the CU's
+// L2 fetch rate).  delta_{t-1} of both sequences is broadcast from LDS ([state][sequence], one
+// ds_read_b128 per row), the four row groups fold by two lane exchanges (the maximum is exact,
+// so the order is free), and one barrier per step publishes delta_t in the other LDS buffer.
+// Arithmetic is trellis_fwd_f64's: fl(d + a), the maximum over i, fl(m + b); an out-of-range
+// observation reads emission row 0 and sets BADOBS.  The two sequences may differ in length
+// (the longer one runs on alone); rows are written FULL (both planes), which the row contract
+// allows for any lo_every.
+namespace {
+__global__ __launch_bounds__(1024) void trellis_few_f64(T64FwdArgs g) {
+  constexpr int NP = 256, K = NP / 4;
+  __shared__ __attribute__((aligned(16))) double dl[2][NP][2];  // [buffer][state][sequence]
+  const int lane = threadIdx.x & 63;
+  const int wv = (int)threadIdx.x >> 6;
+  const int c = lane & 15, rg = lane >> 4;
+  const int j = 16 * wv + c;
+  const int64_t slot = g.seq_begin + 2 * (int64_t)blockIdx.x;
+  const bool two = slot + 1 < g.seq_begin + g.nslots;
+  const int64_t sq0 = g.order ? (int64_t)g.order[slot] : slot;
+  const int64_t sq1 = two ? (g.order ? (int64_t)g.order[slot + 1] : slot + 1) : sq0;
+  const int64_t e0 = g.offsets[sq0], e1 = g.offsets[sq1];
+  const int T0 = (int)(g.offsets[sq0 + 1] - e0);
+  const int T1 = two ? (int)(g.offsets[sq1 + 1] - e1) : 0;
+  const int T = T0 > T1 ? T0 : T1;
+  if (T <= 0) return;  // the backtrack reports empty sequences
+  const sptr<int32_t> ob0 = scalar_view(g.obs + e0);
+  const sptr<int32_t> ob1 = scalar_view(g.obs + e1);
+  uint32_t* __restrict__ rows0 = reinterpret_cast<uint32_t*>(g.delta) + (e0 - g.delta_elem_base) * (2 * NP);
+  uint32_t* __restrict__ rows1 = reinterpret_cast<uint32_t*>(g.delta) + (e1 - g.delta_elem_base) * (2 * NP);
+  const unsigned V = (unsigned)g.nobs;
+  unsigned bad = 0;  // bit 0 / 1: sequence 0 / 1
+  auto em = [&](const sptr<int32_t> ob, int t, unsigned bit) -> double {
+    const unsigned o = (unsigned)ob[t];
+    bad |= (o >= V) ? bit : 0u;
+    return g.et[(size_t)(o < V ? o : 0u) * NP + j];
+  };
+  auto put = [&](uint32_t* rows, int t, double v) {
+    uint32_t* r = rows + (size_t)t * (2 * NP) + j;
+    __builtin_nontemporal_store(hi_word(v), r);
+    __builtin_nontemporal_store(lo_word(v), r + NP);
+  };
+  if (rg == 0) {
+    const double p = g.pi[j];
+    double d0 = ninf_d(), d1 = ninf_d();
+    if (T0 > 0) {
+      d0 = p + em(ob0, 0, 1u);
+      put(rows0, 0, d0);
+    }
+    if (T1 > 0) {
+      d1 = p + em(ob1, 0, 2u);
+      put(rows1, 0, d1);
+    }
+    dl[0][j][0] = d0;
+    dl[0][j][1] = d1;
+  }
+  __syncthreads();
+  const double* __restrict__ acol = g.a + (size_t)rg * NP + j;  // rows rg, rg + 4, ...
+  for (int t = 1; t < T; ++t) {
+    const bool live0 = t < T0, live1 = t < T1;  // block-uniform
+    double b0 = 0.0, b1 = 0.0;
+    if (live0) b0 = em(ob0, t, 1u);
+    if (live1) b1 = em(ob1, t, 2u);
+    const double(*src)[2] = dl[(t - 1) & 1];
+    double m0, m1;
+    {
+      const double a = acol[0];
+      const f64x2 d = *reinterpret_cast<const f64x2*>(src[rg]);
+      m0 = d.x + a;  // s_i = d[i] + a[i,j]  (viterbi.rs:15)
+      m1 = d.y + a;
+    }
+#pragma unroll 21
+    for (int k = 1; k < K; ++k) {
+      const double a = acol[(size_t)k * 4 * NP];
+      const f64x2 d = *reinterpret_cast<const f64x2*>(src[4 * k + rg]);
+      m0 = __builtin_fmax(m0, d.x + a);
+      m1 = __builtin_fmax(m1, d.y + a);
+    }
+    m0 = __builtin_fmax(m0, __shfl_xor(m0, 16));
+    m1 = __builtin_fmax(m1, __shfl_xor(m1, 16));
+    m0 = __builtin_fmax(m0, __shfl_xor(m0, 32));
+    m1 = __builtin_fmax(m1, __shfl_xor(m1, 32));
+    if (rg == 0) {
+      double(*dst)[2] = dl[t & 1];
+      if (live0) {
+        const double dn = m0 + b0;  // (d + a) + b -- viterbi.rs:15-17
+        dst[j][0] = dn;
+        put(rows0, t, dn);
+      }
+      if (live1) {
+        const double dn = m1 + b1;
+        dst[j][1] = dn;
+        put(rows1, t, dn);
+      }
+    }
+    __syncthreads();
+  }
+  if (bad && threadIdx.x == 0) {
+    if (bad & 1u) g.status[sq0] = CVK_SEQ_BADOBS;
+    if (bad & 2u) g.status[sq1] = CVK_SEQ_BADOBS;
+  }
+}
+}  // namespace
+
+// the few-sequence layout's launches (tuning key t64_few: -1 auto, 0 never, 1 whenever supported):
+// the plain row-A0 recurrence at 192 < N <= 256; auto = up to kT64FewMaxSeqs sequences unless
+// t64_s names a layout.  The bound is the measured break-even against the pair-of-waves layouts
+// on 256 CUs (profiles/t64_few_sweep.txt: 3.96 vs 9.41 ms at 387 sequences, 7.9 vs 9.4 at 1,024
+// = two rounds of workgroups, 15.8 vs 9.4 at 2,048)
+constexpr int64_t kT64FewMaxSeqs = 1024;
+bool t64_few_launch(int np, const T64FwdArgs& fa, int64_t nseq) {
+  const bool ext = fa.forced || fa.ranges || fa.reverse || fa.start || fa.row_base || fa.resume_rows ||
+                   fa.slot_order || fa.last_row;
+  if (np != 256 || fa.nslots != nseq || ext || fa.dp_assoc || fa.zero_init || fa.nstates <= 192 || fa.nstates > 256)
+    return false;
+  const int k = tuning().t64_few;
+  return k > 0 || (k < 0 && nseq <= kT64FewMaxSeqs && tuning().t64_s == 0);
+}
+
 int t64_seqs_per_wave(int64_t nseq, int cus, int np) {
   // fill at least two waves per SIMD (4 SIMDs per CU), then prefer the larger S: each A row
   // streamed from L2 serves S sequences.  NP = 512 / 1,024 units are pairs / quads of waves
@@ -2477,6 +2600,10 @@ hipError_t launch_t64_fwd(int np, int s, const T64FwdArgs& fa_in, int64_t nseq, 
   const bool ext = fa.forced || fa.ranges || fa.reverse || fa.start || fa.row_base || fa.resume_rows ||
                    fa.slot_order || fa.last_row;
   if (np == 64 && wave && !fa.dp_assoc && !ext) return launch_t64_wave(fa, nseq, stream);
+  if (t64_few_launch(np, fa, nseq)) {
+    hipLaunchKernelGGL(trellis_few_f64, dim3((unsigned)((nseq + 1) / 2)), dim3(1024), 0, stream, fa);
+    return hipGetLastError();
+  }
   if (np == 512 || np == 1024) {  // batch decode only (t64_batch_states), forced states allowed
     if (fa.ranges || fa.reverse || fa.start || fa.row_base || fa.resume_rows || fa.slot_order || fa.last_row ||
         (fa.dp_assoc && fa.forced))

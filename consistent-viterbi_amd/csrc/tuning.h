@@ -50,7 +50,8 @@ struct Tuning {
   int t64_wg_force = 0;        // 1: the eight-wave layouts whatever the batch's lengths
   int t64_rs = 1;              // 0: small batches' column-split pairs instead of the row split
   int t64_w2 = 1;              // 0: no pair-of-waves small-batch layout
-  int t64_wave = 1;            // 0: N <= 64 on the lock-step kernel instead of one wave per sequence
+  int t64_few = -1;            // NP = 256 few-sequence forward (a CU per two sequences): -1 auto, 0 never, 1 whenever supported
+  int t64_wave = 1;           // 0: N <= 64 on the lock-step kernel instead of one wave per sequence
   int t64_bal = 8;             // steps between SIMD-balancing updates (0: off)
   int t64_cp_s = 0;            // trellis_cp_f64 sequences per wave 1 / 2 / 4 (0: by batch)
   int t64_cp_pf = 0;           // split-column trellis_cp_f64 A rows in flight: 16 (0: 32)
@@ -59,6 +60,8 @@ struct Tuning {
   int t64_lo_every = 8;        // low planes of the delta rows at every K-th row and the last (1: every row; <= 16)
   int t64_fixed_first = 16777216;  // certified fixed-point first pass of the plain f64 batch decode: the fewest
                                // elements (sum of lengths) of a call that takes it (0: never)
+  int t64_fixed_chunks = 8;    // the pass's chunks pipelined over two streams, at least min(this, nseq / 2048)
+                               // (<= 64); 0: back to back on one stream, one chunk under the workspace cap
   // ---- generic and wide kernels (kernels/trellis.hip) ----
   int generic_s = 0;           // sequences per workgroup 1 / 2 / 4 (0: by batch and LDS)
   int generic_split = 0;       // 1: generic_fwd_split (K threads per state)

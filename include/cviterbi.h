@@ -115,7 +115,8 @@ typedef struct cv_timing {
   int64_t launches;      /* forward launches (chunks) */
   int32_t kernel;        /* CV_KERNEL_TRELLIS, _TRELLIS_F64 or _GENERIC actually used */
   int32_t padded_states; /* NP of the trellis kernel (0 for generic) */
-  int32_t mfma_tiles;    /* TRELLIS_F64: sequences per forward wave (last chunk); GENERIC: 0 wide
+  int32_t mfma_tiles;    /* TRELLIS_F64: sequences per forward wave (last chunk), 0 = the few-sequence
+                            layout (two per 16-wave workgroup, key t64_few); GENERIC: 0 wide
                             (each step over many workgroups, N > 10240 f64 / 20480 f32), else -1;
                             -1 otherwise (the field name is kept for ABI stability) */
 } cv_timing;
@@ -195,6 +196,9 @@ CV_API void cv_hmm_destroy(cv_hmm* h);
  *   t64_wg 1              0: one wave per workgroup instead of eight-wave units
  *   t64_wg_force 0        1: eight-wave units whatever the batch's lengths
  *   t64_rs 1 / t64_w2 1   0: no row-split / no pair-of-waves small-batch layout
+ *   t64_few -1            f64 row A0 at 192 < N <= 256: the few-sequence forward (one CU per two
+ *                         sequences, A streamed from L2 once per workgroup-step): -1 auto, 0 never,
+ *                         1 whenever supported
  *   t64_wave 1            0: N <= 64 on the lock-step kernel, not one wave per sequence; 2: N <= 48
  *                         on the 64-state one-wave kernel
  *   t64_bal 8             steps between SIMD-balancing updates (0: off)
@@ -215,6 +219,11 @@ CV_API void cv_hmm_destroy(cv_hmm* h);
  *                         f64 kernels (cv_last_fixed_first_stats).  Such a call waits for its stream
  *                         once.  A handle that left more than 1 in 8 sequences of a call uncertified
  *                         stays on the f64 kernels from then on.  0: never (the earlier behaviour)
+ *   t64_fixed_chunks 8    that pass in chunks pipelined over two streams: at least
+ *                         min(this, sequences / 2048) chunks (<= 64) out of a double-buffered workspace
+ *                         (each chunk half the workspace cap), a chunk's certificate backtrack and score
+ *                         beside the next chunk's forward.  0: the chunks back to back on the caller's
+ *                         stream, one chunk where the batch fits the cap (the earlier schedule)
  *   generic_s 0           generic kernels' sequences per workgroup 1 / 2 / 4 (0: by batch)
  *   generic_split 0, generic_split_k 0   1: K threads per state (generic_fwd_split), its K
  *   generic_wide 1, generic_wide_min 0   0: never wide / > 0: wide from this N
