@@ -1056,28 +1056,40 @@ __global__ __launch_bounds__(NP * 4) void trellis_fwd2_i32(FixFwdArgs args) {
     if (threadIdx.x == 0) mus[(t + 1) % 3] = INT32_MIN;
     if (KB > 1) ld8(dsrc + 8, Q);
     int m0a = 0, m0b = 0, m1a = 0, m1b = 0;
-    auto rows4 = [&](const int4& dd, int k, bool init) {
-      const int s00 = dd.x + a_reg[2 * k + 0], s01 = dd.x + a_reg[2 * k + 1];
-      const int s10 = dd.y + a_reg[2 * k + 2], s11 = dd.y + a_reg[2 * k + 3];
-      const int s20 = dd.z + a_reg[2 * k + 4], s21 = dd.z + a_reg[2 * k + 5];
-      const int s30 = dd.w + a_reg[2 * k + 6], s31 = dd.w + a_reg[2 * k + 7];
-      if (init) {
-        m0a = max(s00, s10);
-        m1a = max(s01, s11);
-        m0b = max(s20, s30);
-        m1b = max(s21, s31);
-      } else {
-        m0a = max(max(m0a, s00), s10);
-        m1a = max(max(m1a, s01), s11);
-        m0b = max(max(m0b, s20), s30);
-        m1b = max(max(m1b, s21), s31);
+    // One 8-row block: its 16 sums first, then the 8 maxima (tools/microbench/i32_mix_rates.hip,
+    // MIX_K16: the integer mix issues faster in runs of one kind than interleaved).
+    auto rows8 = [&](const int4 (&B)[2], int k, bool init) {
+      int s[16];
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        const int d = r < 4 ? (&B[0].x)[r] : (&B[1].x)[r - 4];
+        s[2 * r + 0] = d + a_reg[2 * k + 2 * r + 0];
+        s[2 * r + 1] = d + a_reg[2 * k + 2 * r + 1];
       }
+      // The scheduler would interleave them again; two empty asm statements that pass the sums
+      // through keep every maximum (each takes one sum of either half) behind all 16 adds.
+      asm volatile("" : "+v"(s[0]), "+v"(s[1]), "+v"(s[2]), "+v"(s[3]), "+v"(s[4]), "+v"(s[5]), "+v"(s[6]), "+v"(s[7]));
+      asm volatile("" : "+v"(s[8]), "+v"(s[9]), "+v"(s[10]), "+v"(s[11]), "+v"(s[12]), "+v"(s[13]), "+v"(s[14]), "+v"(s[15]));
+      if (init) {
+        m0a = max(s[0], s[8]);
+        m1a = max(s[1], s[9]);
+        m0b = max(s[4], s[12]);
+        m1b = max(s[5], s[13]);
+      } else {
+        m0a = max(max(m0a, s[0]), s[8]);
+        m1a = max(max(m1a, s[1]), s[9]);
+        m0b = max(max(m0b, s[4]), s[12]);
+        m1b = max(max(m1b, s[5]), s[13]);
+      }
+      m0a = max(max(m0a, s[2]), s[10]);
+      m1a = max(max(m1a, s[3]), s[11]);
+      m0b = max(max(m0b, s[6]), s[14]);
+      m1b = max(max(m1b, s[7]), s[15]);
     };
 #pragma unroll
     for (int k = 0; k < KB; ++k) {
       int4(&B)[2] = (k & 1) ? Q : P;
-      rows4(B[0], 8 * k, k == 0);
-      rows4(B[1], 8 * k + 4, false);
+      rows8(B, 8 * k, k == 0);
       __builtin_amdgcn_sched_barrier(0);
       if (k + 2 < KB)
         ld8(dsrc + 8 * (k + 2), B);
