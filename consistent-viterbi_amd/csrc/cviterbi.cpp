@@ -1920,6 +1920,7 @@ CV_API cv_status cv_hmm_set_tuning(cv_hmm* h, const char* key, int64_t value) {
   if (std::strcmp(key, "t64_nonpos") == 0) {  // model_nonpos reads it: rebuild the f64 trellis tables
     h->nonpos_cache = -1;
     h->t64_ready = false;
+    h->fx_state = -1;  // ensure_fix_tables reads it too: the fixed-point first pass follows the key
   }
   return CV_OK;
 }

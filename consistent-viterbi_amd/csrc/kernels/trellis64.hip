@@ -2698,21 +2698,32 @@ hipError_t bt_pf(int np, const T64BtArgs& ba, dim3 grid, dim3 block, hipStream_t
   return bt_pf_np<PF, false>(np, ba, grid, block, stream);
 }
 
+// backtrack_f64's rows in flight for tuning key t64_bt_pf, total in the key: the deepest
+// instantiated depth (2, 4, 8, 16, 32) not above the request and not above the layout's cap --
+// 32 at NP = 64 only, 16 up to NP = 256 (the sparse-low-plane kernel's cap too: it runs at
+// 128 <= NP <= 256), 8 at NP = 512, 4 at NP = 1,024 (the ring's registers); a request below 2
+// (0 included) is the default by NP
+static int t64_bt_depth(int np, int key) {
+  if (key < 2) return np >= 192 ? 2 : np == 64 ? 32 : 8;
+  const int cap = np == 64 ? 32 : np <= 256 ? 16 : np <= 512 ? 8 : 4;
+  int pf = 2;
+  while (pf * 2 <= key && pf * 2 <= cap) pf *= 2;
+  return pf;
+}
+
 hipError_t launch_t64_bt(int np, const T64BtArgs& ba, int64_t nseq, hipStream_t stream) {
   if (nseq <= 0) return hipSuccess;
   const dim3 grid((unsigned)((nseq + 3) / 4)), block(256);
   // NP = 64 (configs 2/3): the longest chains set the makespan and each step's hi row (256 B)
   // comes from HBM: 32 rows in flight, config 3 backtrack 0.615 -> 0.51 ms (16: 0.54)
   // (profiles/r02_ab_bt_pf_c3.txt); N = 256: occupancy matters more (2 rows, 8 waves/SIMD);
-  // tuning key t64_bt_pf (bit-identical) sets 2, 4, 8, 16 or 32
-  const int pf_key = tuning().t64_bt_pf;
-  const int pf = pf_key ? pf_key : np >= 192 ? 2 : np == 64 ? 32 : 8;
-  switch (pf) {
+  // tuning key t64_bt_pf (bit-identical) asks for 2, 4, 8, 16 or 32
+  switch (t64_bt_depth(np, tuning().t64_bt_pf)) {
     case 2: return bt_pf<2>(np, ba, grid, block, stream);
     case 4: return bt_pf<4>(np, ba, grid, block, stream);
+    case 8: return bt_pf<8>(np, ba, grid, block, stream);
     case 16: return bt_pf<16>(np, ba, grid, block, stream);
-    case 32: return np == 64 ? bt_pf<32>(np, ba, grid, block, stream) : hipErrorInvalidValue;
-    default: return bt_pf<8>(np, ba, grid, block, stream);
+    default: return bt_pf<32>(np, ba, grid, block, stream);
   }
 }
 

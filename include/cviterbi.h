@@ -205,7 +205,10 @@ CV_API void cv_hmm_destroy(cv_hmm* h);
  *   t64_cp_s 0            trellis_cp_f64 sequences per wave 1 / 2 / 4 (0: by batch)
  *   t64_cp_w 0            trellis_cp_f64 waves splitting the columns: 1 never, > 1 always (0: up to
  *                         4,096 sequences, NP >= 128); t64_cp_pf 0: its A rows in flight 32 (16)
- *   t64_bt_pf 0           backtrack_f64 rows in flight 2 / 4 / 8 / 16 / 32 (0: by NP)
+ *   t64_bt_pf 0           backtrack_f64 rows in flight 2 / 4 / 8 / 16 / 32 (0: by NP).  Any value is
+ *                         accepted: the deepest of these depths not above the request that the layout
+ *                         has (32 at NP = 64 only, at most 16 up to NP = 256 and for the sparse low
+ *                         planes, 8 at NP = 512, 4 at NP = 1,024); a request below 2: by NP
  *   t64_lo_every 8        cv_decode_batch[_device], f64 row A0 on log-probability models, 64 < N <= 256:
  *                         the forward pass writes the low words of its delta rows at every K-th row
  *                         and the last row only (K <= 16; 1: at every row, the earlier behaviour), and

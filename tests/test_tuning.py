@@ -124,6 +124,27 @@ def test_env_after_create_does_not_change_kernel(gpu, monkeypatch):
         np.testing.assert_array_equal(x, y)
 
 
+def test_every_key_is_named_by_a_gpu_test():
+    """Every tuning key is "bit-identical in results" (csrc/tuning.h), so every key needs a test
+    that sets it on a GPU and compares the result: each name appears as a whole word in a
+    tests/test_gpu_*.py, tests/handle_ops.py or tests/test_fit.py.  A key added later cannot
+    arrive untested; an exemption is a reason written here."""
+    exempt = {"trace": "host phase stamps on stderr only: no kernel, layout or schedule reads it"}
+    tests = os.path.join(ROOT, "tests")
+    names = sorted(f for f in os.listdir(tests)
+                   if (f.startswith("test_gpu_") and f.endswith(".py")) or f in ("handle_ops.py", "test_fit.py"))
+    assert len(names) >= 20, names
+    text = "\n".join(open(os.path.join(tests, f)).read() for f in names)
+    keys = cv.tuning_keys()
+    assert set(exempt) <= set(keys), sorted(set(exempt) - set(keys))
+    # by name, or by its variable where a test hands the key to a child process (CV_<KEY>)
+    def named(k):
+        return re.search(r"\b(?:%s|CV_%s)\b" % (re.escape(k), re.escape(k.upper())), text) is not None
+
+    missing = sorted(k for k in keys if k not in exempt and not named(k))
+    assert not missing, f"tuning keys no GPU test names: {missing}"
+
+
 def test_every_key_documented_in_the_header():
     """Every tuning key the library knows is listed in include/cviterbi.h's tuning-key table (the
     documented survivors of VERDICT r5 #5), every key has its line."""
