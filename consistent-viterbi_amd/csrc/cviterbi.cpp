@@ -5385,6 +5385,10 @@ CV_API cv_status cv_solver_write_cfn(cv_solver* s, const char* path, uint64_t* c
   if (s->ncomp > k)
     return set_err(CV_EUNSUPPORTED, "component %d >= %d active components: cfn.rs:118 indexes out of bounds",
                    s->ncomp - 1, k);
+  // the kernel keeps two rows of N doubles in LDS (160 KiB per workgroup on gfx950)
+  if (N > cvcfn::kCfnMaxStates)
+    return set_err(CV_EUNSUPPORTED, "CFN export supports at most %d states (two f64 rows in LDS), model has %d",
+                   cvcfn::kCfnMaxStates, N);
   // jobs: every boundary pair x start state, the end cost per state, the start cost
   std::vector<cvcfn::CfnJob> jobs;
   const int64_t nb = (int64_t)bnd.size();
@@ -5501,9 +5505,11 @@ CV_API cv_status cv_solver_write_cfn(cv_solver* s, const char* path, uint64_t* c
     out += "}, \n";
     for (int32_t j = i + 1; j < k; ++j) {
       const double* t = tab.data() + ((size_t)i * k + j) * NN;
-      bool nonzero = false;
-      for (size_t q = 0; q < NN && !nonzero; ++q) nonzero = t[q] != 0.0;  // tcost.sum() != 0.0 (costs <= 0)
-      if (!nonzero) continue;
+      // tcost.sum() != 0.0 (cfn.rs:196), summed left to right as the checker does: a table of a
+      // model with positive entries can hold +1 and -1 and is then left out like any zero table
+      double sum = 0.0;
+      for (size_t q = 0; q < NN; ++q) sum += t[q];
+      if (sum == 0.0) continue;
       out += "\t\tf" + std::to_string(i) + "_" + std::to_string(j) + ": { scope: [n" + std::to_string(i) + ", n" +
              std::to_string(j) + "], costs: ";
       vec_text(t, NN);

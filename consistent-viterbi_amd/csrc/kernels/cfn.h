@@ -12,6 +12,10 @@ constexpr int32_t kCfnSegment = 0;  // longest_path (cfn.rs:11-34): start (t_beg
 constexpr int32_t kCfnEnd = 1;      // get_unary_end_cost (cfn.rs:55-80): same, forced through t_end
 constexpr int32_t kCfnStart = 2;    // get_unary_start_cost (cfn.rs:36-53): init_probs at t_begin
 
+// two rows of N doubles fill the 160 KiB of LDS a gfx950 workgroup can have at N = 10,240;
+// cv_solver_write_cfn refuses larger models before it uploads or launches anything
+constexpr int kCfnMaxStates = 10240;
+
 struct CfnJob {
   int64_t t_begin, t_end;  // super-sequence element range; the row at t_end is the output
   int32_t state;           // start state (unused for kCfnStart)

@@ -58,9 +58,11 @@ __global__ __launch_bounds__(256) void cfn_rows_f64(CfnArgs g) {
 hipError_t launch_cfn_rows(const CfnArgs& g, int64_t njobs, hipStream_t stream) {
   if (njobs <= 0) return hipSuccess;
   const size_t lds = 2 * (size_t)g.nstates * sizeof(double);
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cfn_rows_f64), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
+  if (lds > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cfn_rows_f64),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
   hipLaunchKernelGGL(cfn_rows_f64, dim3((unsigned)njobs), dim3(256), lds, stream, g);
   return hipGetLastError();
 }

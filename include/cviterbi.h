@@ -693,7 +693,8 @@ CV_API void cv_solver_destroy(cv_solver* s);
  * computed on the GPU in f64, bit-identical to the reference loops), the lower bound, in the
  * reference's text layout and float formatting.  *compile_ms = table time (the value main.rs
  * writes when run_cfn is set, main.rs:116-118).  Cost: (boundaries x N) segment passes of
- * N^2 per element, as in the reference -- meant for the problem sizes toulbar2 takes. */
+ * N^2 per element, as in the reference -- meant for the problem sizes toulbar2 takes.
+ * At most 10,240 states (two f64 rows in LDS): CV_EUNSUPPORTED above, before any upload. */
 CV_API cv_status cv_solver_write_cfn(cv_solver* s, const char* path, uint64_t* compile_ms);
 
 /* ---- HMM fitting (hmm.rs:30-190) ------------------------------------
