@@ -5629,11 +5629,26 @@ CV_API cv_status cv_hmm_fit_mle(int32_t nstates, int64_t nobs, int64_t nseq, con
   return CV_OK;
 }
 
+// how the calling thread's last cv_hmm_fit_train split its corpus (cv_hmm_fit_last_stats):
+// chunks, max_chunk_elems, pairs_per_wave_max, scratch_batches, family
+constexpr int kFitStats = 5;
+static thread_local int64_t t_fit_last[kFitStats] = {0, 0, 0, 0, 0};
+
+CV_API int32_t cv_hmm_fit_last_stats(int64_t* out, int32_t n) {
+  if (n < 0 || (n > 0 && !out)) {
+    set_err(CV_EINVAL, "bad argument");
+    return -1;
+  }
+  for (int32_t q = 0; q < n && q < kFitStats; ++q) out[q] = t_fit_last[q];
+  return kFitStats;
+}
+
 CV_API cv_status cv_hmm_fit_train(int32_t nstates, int64_t nobs, int64_t nseq, const int64_t* offsets,
                                   const int32_t* obs, const int32_t* tags, int32_t max_iter, double tol,
                                   int32_t device, double* pi, double* a, double* b, int32_t* iters_out) {
   const int32_t N = nstates;
   const int64_t V = nobs;
+  for (int64_t& x : t_fit_last) x = 0;
   cv_status st = fit_validate(N, V, nseq, offsets, obs, tags, false, pi, a, b);
   if (st != CV_OK) return st;
   if (N > cvf::kBwMaxStates) return set_err(CV_EUNSUPPORTED, "Baum-Welch covers N <= %d (N=%d)", cvf::kBwMaxStates, N);
@@ -5665,9 +5680,11 @@ CV_API cv_status cv_hmm_fit_train(int32_t nstates, int64_t nobs, int64_t nseq, c
     (void)hipGetLastError();
     free_b = 0;
   }
-  const int64_t cap_elems = std::max<int64_t>(
-      std::max<int64_t>((2ll << 30) / (8 * N), 1),
-      N > cvf::kBwWaveStates ? (int64_t)(free_b / 2 / (16 * (size_t)N)) : 0);
+  // tuning key bw_chunk_elems > 0 replaces the cap (tests: several chunks on a small corpus)
+  const int64_t cap_elems = tun.bw_chunk_elems > 0
+                                ? (int64_t)tun.bw_chunk_elems
+                                : std::max<int64_t>(std::max<int64_t>((2ll << 30) / (8 * N), 1),
+                                                    N > cvf::kBwWaveStates ? (int64_t)(free_b / 2 / (16 * (size_t)N)) : 0);
   int64_t max_chunk = 0;
   std::vector<std::pair<int64_t, int64_t>> chunks;
   for (int64_t s0 = 0; s0 < nseq;) {
@@ -5677,6 +5694,8 @@ CV_API cv_status cv_hmm_fit_train(int32_t nstates, int64_t nobs, int64_t nseq, c
     max_chunk = std::max(max_chunk, off0[s1] - off0[s0]);
     s0 = s1;
   }
+  t_fit_last[0] = (int64_t)chunks.size();
+  t_fit_last[1] = max_chunk;
   if ((st = d.alpha.ensure((size_t)max_chunk * N * 8)) != CV_OK) return st;
   // beta rows only for the workgroup kernels (N > 64, or CV_BW_GEMM_PATH=1); the one-wave
   // backward never stores beta
@@ -5697,7 +5716,8 @@ CV_API cv_status cv_hmm_fit_train(int32_t nstates, int64_t nobs, int64_t nseq, c
   if ((st = d.dump.ensure((size_t)cvf::kBwDumpWaves * 64 * 8)) != CV_OK) return st;
   int cus = 0;
   HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-  const int64_t max_waves = (int64_t)std::max(cus, 1) * 8;  // backward waves resident at 2 per SIMD
+  // backward waves resident at 2 per SIMD (tuning key bw_max_waves > 0: that many, tests)
+  const int64_t max_waves = tun.bw_max_waves > 0 ? (int64_t)tun.bw_max_waves : (int64_t)std::max(cus, 1) * 8;
   {
     // parameters go to the device once and stay there (M-step on the device)
     std::vector<double> at((size_t)N * N), et((size_t)V * N);
@@ -5805,9 +5825,13 @@ CV_API cv_status cv_hmm_fit_train(int32_t nstates, int64_t nobs, int64_t nseq, c
       g.b_num = A + 3 * N;
       g.xi_s = g.b_num + (size_t)V * N;
       g.xi_zero = g.xi_s + (size_t)N * N;
+      cvf::BwEstepInfo info;
       const hipError_t e =
-          cvf::launch_bw_estep(g, c.second - c.first, max_waves, ss, off0[c.second] - off0[c.first], nullptr);
+          cvf::launch_bw_estep(g, c.second - c.first, max_waves, ss, off0[c.second] - off0[c.first], nullptr, &info);
       if (e != hipSuccess) return set_err(CV_EDEVICE, "Baum-Welch launch failed: %s", hipGetErrorString(e));
+      t_fit_last[2] = std::max(t_fit_last[2], info.pairs_per_wave);
+      t_fit_last[3] = std::max(t_fit_last[3], info.scratch_batches);
+      t_fit_last[4] = info.family;
     }
     // M-step (hmm.rs:145-170) on the device: new_pi = sum gamma_0 / R; new_a = sum xi / a_den
     // (row); new_b = sum gamma at o / b_den; sum_t xi_t = A o S + z / N^2 (see bw_stats);

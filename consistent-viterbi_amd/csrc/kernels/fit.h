@@ -84,8 +84,16 @@ hipError_t launch_mle_counts(const MleArgs& g, int64_t nseq, hipStream_t stream)
 // nrows: the chunk's elements (alpha / beta rows from elem_base), for the GEMM path (N > 128)
 // fwd_done (64 < N <= 256, the matrix-core kernels): recorded on `stream` right after the
 // forward launch when non-null
+// info (nullable): what the launch ran, written by the branch that launched it
+enum BwFamily { kBwFamNone = 0, kBwFamWave = 1, kBwFamPerSeq = 2, kBwFamMm = 3, kBwFamStrided = 4, kBwFamStridedGlobal = 5 };
+struct BwEstepInfo {
+  int family = kBwFamNone;      // one-wave kernels, per-sequence workgroup kernels (vectors in LDS), matrix-core
+                                // kernels, strided kernels in LDS / in global scratch
+  int64_t pairs_per_wave = 0;   // one-wave backward: pairs of sequences its busiest wave walks
+  int64_t scratch_batches = 0;  // strided kernels in global scratch: launches of kBwScratchSeqs sequences
+};
 hipError_t launch_bw_estep(const BwArgs& g, int64_t nseq, int64_t max_waves, hipStream_t stream, int64_t nrows,
-                           hipEvent_t fwd_done = nullptr);
+                           hipEvent_t fwd_done = nullptr, BwEstepInfo* info = nullptr);
 // the E-step runs the matrix-core kernels (64 < N <= 256; tuning key bw_perseq = 1: not)
 bool bw_estep_mm(int nstates);
 // tuning key bw_gemm_path = 1: the per-sequence kernels + xi GEMM at every N (A/B and tests;

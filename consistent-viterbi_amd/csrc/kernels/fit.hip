@@ -1007,7 +1007,9 @@ __device__ __forceinline__ void mm_setup(const BwArgs& g, int64_t nseq, int64_t*
   const int tid = threadIdx.x;
   if (tid < G) {
     const int64_t k = (int64_t)blockIdx.x * G + tid;
-    int64_t e0 = 0;
+    // a slot without a sequence (T = 0) points at the chunk's first row: bw_bwd_mm loads alpha
+    // rows unconditionally, and element 0 lies elem_base rows BELOW a later chunk's workspace
+    int64_t e0 = g.elem_base;
     int T = 0;
     if (k < nseq) {
       const int64_t s = g.order ? g.order[k] : k;
@@ -1461,12 +1463,17 @@ bool bw_estep_mm(int nstates) { return nstates > kBwWaveStates && nstates <= kBw
 bool bw_gemm_path() { return cvk::tuning().bw_gemm_path == 1; }
 
 hipError_t launch_bw_estep(const BwArgs& g, int64_t nseq, int64_t max_waves, hipStream_t stream, int64_t nrows,
-                           hipEvent_t fwd_done) {
+                           hipEvent_t fwd_done, BwEstepInfo* info) {
+  BwEstepInfo none;
+  BwEstepInfo& inf = info ? *info : none;
+  inf = BwEstepInfo{};
   if (nseq <= 0) return hipSuccess;
   if (g.nstates > kBwMaxStates) return hipErrorInvalidValue;
   if (g.nstates > kBwMmStates) {  // N > 256: the strided per-sequence kernels, then the xi GEMM
     if (g.gscratch) {  // their vectors in global scratch, kBwScratchSeqs sequences per launch
+      inf.family = kBwFamStridedGlobal;
       for (int64_t s0 = 0; s0 < nseq; s0 += kBwScratchSeqs) {
+        ++inf.scratch_batches;
         BwArgs gb = g;
         gb.offsets = g.offsets + s0;  // rows stay at (element - elem_base)
         const unsigned n = (unsigned)std::min<int64_t>(kBwScratchSeqs, nseq - s0);
@@ -1476,6 +1483,7 @@ hipError_t launch_bw_estep(const BwArgs& g, int64_t nseq, int64_t max_waves, hip
       }
     } else {  // in LDS (N <= kBwLdsMaxStates)
       if (g.nstates > kBwLdsMaxStates) return hipErrorInvalidValue;
+      inf.family = kBwFamStrided;
       const size_t l1 = (size_t)g.nstates * 8, l4 = 4 * l1;
       for (const void* k :
            {reinterpret_cast<const void*>(&bw_forward_g<false>), reinterpret_cast<const void*>(&bw_backward_g<false>)})
@@ -1505,7 +1513,9 @@ hipError_t launch_bw_estep(const BwArgs& g, int64_t nseq, int64_t max_waves, hip
       if (g.nstates <= 128) launch_mm<128, 2, 4, 4>(g, nseq, stream, fwd_done);
       else if (g.nstates <= 192) launch_mm<192, 2, 4, 4>(g, nseq, stream, fwd_done);
       else launch_mm<256, 2, 4, 4>(g, nseq, stream, fwd_done);
+      inf.family = kBwFamMm;
     } else {
+      inf.family = kBwFamPerSeq;
       hipLaunchKernelGGL(bw_forward, dim3((unsigned)nseq), dim3(256), 0, stream, g);
       hipLaunchKernelGGL(bw_backward, dim3((unsigned)nseq), dim3(256), 0, stream, g);
       hipLaunchKernelGGL(bw_stats_rows, dim3((unsigned)nseq), dim3(256), 0, stream, g);
@@ -1538,8 +1548,11 @@ hipError_t launch_bw_estep(const BwArgs& g, int64_t nseq, int64_t max_waves, hip
     else if (g.nstates <= 32) launch_wave_estep<32>(g, nseq, nwaves, stream);
     else if (g.nstates <= 48) launch_wave_estep<48>(g, nseq, nwaves, stream);
     else launch_wave_estep<64>(g, nseq, nwaves, stream);
+    inf.family = kBwFamWave;
+    inf.pairs_per_wave = ((nseq + 1) / 2 + nwaves - 1) / nwaves;
     return hipGetLastError();
   }
+  inf.family = kBwFamPerSeq;
   hipLaunchKernelGGL(bw_forward, dim3((unsigned)nseq), dim3(256), 0, stream, g);
   hipLaunchKernelGGL(bw_backward, dim3((unsigned)nseq), dim3(256), 0, stream, g);
   const size_t lds = ((size_t)g.nstates * g.nstates + 256 + 4) * sizeof(double);

@@ -6,8 +6,11 @@
 // cv_hmm_set_tuning.  A caller's stray CV_* variable set after the handle exists changes
 // nothing.  The host API copies the handle's snapshot into a thread-local (tuning_enter) for
 // the duration of a call, so the kernel launchers read plain fields instead of the environment.
-// Every key is bit-identical in results (layouts, schedules, A/B paths); none changes what a
-// decode returns.  Handle-less entry points (cv_hmm_fit_*) snapshot the environment per call.
+// Every decode key is bit-identical in results (layouts, schedules, A/B paths); none changes
+// what a decode returns.  The fitting keys (bw_*) are not bit-identical: the E-step sums are
+// f64 atomic adds in arrival order, so another path, chunking or wave count adds the same terms
+// in another order; they hold to the fitting tolerance (1e-9 on the log10 parameters, as
+// against the oracle).  Handle-less entry points (cv_hmm_fit_*) snapshot the environment per call.
 #pragma once
 
 #include <cstdint>
@@ -78,6 +81,10 @@ struct Tuning {
   int bw_global = 0;           // 1: the strided kernels' vectors in global scratch from N = 257
   int bw_perseq = 0;           // 1: the per-sequence E-step kernels at 64 < N <= 256
   int bw_gemm_path = 0;        // 1: the xi GEMM path at every N
+  int bw_chunk_elems = 0;      // > 0: the most elements (alpha / beta rows) of a chunk of sequences, instead
+                               // of the memory rule (a longer sequence is still a chunk of its own)
+  int bw_max_waves = 0;        // > 0: the most backward waves of the N <= 64 kernels (0: 8 per CU); each
+                               // wave walks ceil(pairs / waves) pairs of sequences
 };
 
 // the current call's tuning: the handle's snapshot inside a host API call, else the defaults

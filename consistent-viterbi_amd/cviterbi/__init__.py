@@ -10,7 +10,7 @@ from .decode import (constrained_pairs, constrained_partials, constrained_select
                      timing_end)
 from .emissions import decode_emissions, decode_emissions_device  # noqa: F401
 from .emissions import posterior_emissions, posterior_emissions_device, score_emissions  # noqa: F401
-from .fit import fit_mle, fit_train  # noqa: F401
+from .fit import fit_mle, fit_train, last_fit_stats  # noqa: F401
 from .kbest import kbest_batch, kbest_batch_device  # noqa: F401
 from .posterior import posterior_batch, posterior_batch_device, score_batch  # noqa: F401
 from .sample import sample_batch, sample_batch_device, uniform  # noqa: F401

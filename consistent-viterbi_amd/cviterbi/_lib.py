@@ -47,7 +47,7 @@ EXPORTS = [
     "cv_decode_emissions", "cv_decode_emissions_device",
     "cv_posterior_emissions", "cv_posterior_emissions_device",
     "cv_sample_batch", "cv_sample_batch_device",
-    "cv_last_t64_stats", "cv_last_fixed_first_stats",
+    "cv_last_t64_stats", "cv_last_fixed_first_stats", "cv_hmm_fit_last_stats",
 ]
 
 
@@ -162,6 +162,7 @@ def lib():
         "cv_solver_write_cfn": ([P, ctypes.c_char_p, P], S),
         "cv_hmm_fit_mle": ([I32, I64, I64, P, P, P, I32, P, P, P], S),
         "cv_hmm_fit_train": ([I32, I64, I64, P, P, P, I32, D, I32, P, P, P, P], S),
+        "cv_hmm_fit_last_stats": ([P, I32], I32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

@@ -49,3 +49,22 @@ def fit_train(pi, a, b, offsets, obs, tags, max_iter=1000, tol=0.001, device=0):
     L.check(L.lib().cv_hmm_fit_train(n, v, len(offsets) - 1, _p(offsets), _p(obs), _p(tags), int(max_iter),
                                      float(tol), int(device), _p(pi), _p(a), _p(b), ctypes.byref(it)))
     return pi, a, b, it.value
+
+
+FIT_STATS = ("chunks", "max_chunk_elems", "pairs_per_wave_max", "scratch_batches", "family")
+FIT_FAMILIES = {0: None, 1: "wave", 2: "perseq", 3: "mm", 4: "strided", 5: "strided_global"}
+
+
+def last_fit_stats():
+    """How this thread's last fit_train split its corpus (cv_hmm_fit_last_stats): chunks of
+    sequences, the largest chunk's elements, the most pairs of sequences one backward wave walked
+    (N <= 64, else 0), the most global-scratch launches per chunk (else 0), and the E-step kernel
+    family by name (FIT_FAMILIES; "family_code" keeps the number)."""
+    out = (ctypes.c_int64 * len(FIT_STATS))()
+    n = L.lib().cv_hmm_fit_last_stats(out, len(FIT_STATS))
+    if n < len(FIT_STATS):
+        raise L.CVError(L.CV_EINTERNAL, f"cv_hmm_fit_last_stats returned {n} words")
+    d = {k: int(out[q]) for q, k in enumerate(FIT_STATS)}
+    d["family_code"] = d["family"]
+    d["family"] = FIT_FAMILIES.get(d["family_code"], d["family_code"])
+    return d

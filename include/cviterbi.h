@@ -153,7 +153,8 @@ CV_API void cv_hmm_destroy(cv_hmm* h);
 /* HMM::nstates (hmm.rs:207-209). */
 /* ---- tuning keys (per handle) ------------------------------------------------------------
  * Layout, schedule and A/B choices of the kernels, and the test hooks that force a code path.
- * None changes a result: every key is bit-identical in paths, scores and statuses.  Each handle
+ * None changes a decode's result: every key is bit-identical in paths, scores and statuses (the
+ * fitting keys bw_*: to the fitting tolerance, see the end of the list).  Each handle
  * holds ONE snapshot, taken at cv_hmm_create / cv_hmm_from_json from the environment
  * (variable CV_<KEY> in upper case, e.g. CV_T64_S=4 for "t64_s"; integers) over the defaults
  * below, and changed afterwards only by cv_hmm_set_tuning: an environment variable set after
@@ -238,6 +239,13 @@ CV_API void cv_hmm_destroy(cv_hmm* h);
  *   f32_onebar 1          0: two barriers per step in the f32 pair trellis
  *   bw_global 0, bw_perseq 0, bw_gemm_path 0   Baum-Welch: global scratch from N = 257 /
  *                         per-sequence E-step kernels / the xi GEMM path at every N
+ *   bw_chunk_elems 0      Baum-Welch: > 0 the most elements (alpha / beta rows) of a chunk of
+ *                         sequences, instead of the device-memory rule; a longer sequence is still a
+ *                         chunk of its own (test hook: several chunks on a small corpus)
+ *   bw_max_waves 0        Baum-Welch, N <= 64: > 0 the most backward waves (0: 8 per compute unit);
+ *                         each walks ceil(pairs / waves) pairs of sequences (test hook)
+ * The bw_* keys are not bit-identical: the E-step sums are f64 atomic adds in arrival order, so
+ * they hold to the fitting tolerance (1e-9 on the log10 parameters) instead.
  * Unknown keys and values outside int32 are CV_EINVAL.  cv_tuning_key(i) lists the keys
  * (NULL past the last). */
 /* Frees the handle's decode workspaces (delta rows, the posterior and sampling paths' forward rows, the K-best back-pointers and last lists, the
@@ -719,6 +727,17 @@ CV_API cv_status cv_hmm_fit_mle(int32_t nstates, int64_t nobs, int64_t nseq, con
 CV_API cv_status cv_hmm_fit_train(int32_t nstates, int64_t nobs, int64_t nseq, const int64_t* offsets,
                                   const int32_t* obs, const int32_t* tags, int32_t max_iter, double tol,
                                   int32_t device, double* pi, double* a, double* b, int32_t* iters_out);
+/* How the calling thread's last cv_hmm_fit_train split its corpus (thread-local; all 0 before the
+ * first call and after a call that failed before planning).  Length-checked like
+ * cv_last_t64_stats: writes min(n, count) words and returns count (5 now), -1 on a bad argument
+ * (out may be NULL when n is 0).  Words: 0 chunks of sequences (alpha / beta rows are kept for one
+ * chunk at a time); 1 elements of the largest chunk; 2 N <= 64 one-wave kernels: the most pairs
+ * of sequences one backward wave walked, ceil(ceil(sequences / 2) / waves) of the chunk with the
+ * most sequences (else 0); 3 strided kernels in global scratch: the most launches per chunk (else
+ * 0); 4 the E-step kernels that ran: 1 one wave per sequence, 2 one workgroup per sequence
+ * (vectors in LDS), 3 matrix cores (32 sequences per workgroup), 4 strided in LDS, 5 strided in
+ * global scratch, 0 none (max_iter 0). */
+CV_API int32_t cv_hmm_fit_last_stats(int64_t* out, int32_t n);
 
 #ifdef __cplusplus
 }

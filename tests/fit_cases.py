@@ -1,6 +1,7 @@
 """Shared pieces of the fitting tests (tests/test_fit.py, tests/test_gpu_fit_sparse.py,
-tests/golden/make_fit_golden.py): the comparison of two (pi, a, b) triples and the sparse
-model / corpus families S1-S4.
+tests/test_gpu_fit_chunks.py, tests/golden/make_fit_golden.py): the comparison of two
+(pi, a, b) triples, the sparse model / corpus families S1-S4, a corpus of thousands of short
+sequences, and cv_hmm_fit_train's host-side splitting rules restated (chunks, pairs per wave).
 
   S1  fallback-heavy: banded A, half of B zero, every other pi zero, random observations
       and 30% random tags -- alpha, beta, gamma and xi all hit normalize()'s zero-sum
@@ -164,7 +165,69 @@ def dense(n, v, nseq, tmax, seed):
     return pi, a, b, off, obs, tags
 
 
-FAMILIES = {"s1": s1, "s2": s2, "s3": s3, "s4": s4, "dense": dense}
+def short(n, v, nseq, tmax, seed):
+    """-> (pi, a, b, offsets, obs, tags): strictly positive parameters, lengths uniform in
+    1..tmax, 20% random tags -- thousands of sequences in a few elements each (more pairs of
+    sequences than a device has backward waves)."""
+    rng = np.random.default_rng(seed)
+    a = rng.random((n, n))
+    a /= a.sum(axis=1, keepdims=True)
+    b = rng.random((n, v))
+    b /= b.sum(axis=1, keepdims=True)
+    pi = rng.random(n)
+    pi /= pi.sum()
+    off = np.zeros(nseq + 1, np.int64)
+    np.cumsum(rng.integers(1, tmax + 1, size=nseq), out=off[1:])
+    total = int(off[-1])
+    obs = rng.integers(0, v, size=total).astype(np.int32)
+    tags = rng.integers(0, n, size=total).astype(np.int32)
+    tags = np.where(rng.random(total) < 0.2, tags, -1).astype(np.int32)
+    return pi, a, b, off, obs, tags
+
+
+FAMILIES = {"s1": s1, "s2": s2, "s3": s3, "s4": s4, "dense": dense, "short": short}
+
+
+# ---- the host's splitting rules (cv_hmm_fit_train), restated for the tests that hook them -------
+def greedy_chunks(off, cap):
+    """The chunks [s0, s1) of sequences cv_hmm_fit_train forms under a cap of `cap` elements:
+    greedily as many whole sequences as fit; a sequence longer than the cap is a chunk of its own."""
+    off = np.asarray(off, np.int64)
+    nseq = len(off) - 1
+    chunks = []
+    s0 = 0
+    while s0 < nseq:
+        s1 = s0 + 1
+        while s1 < nseq and off[s1 + 1] - off[s0] <= cap:
+            s1 += 1
+        chunks.append((s0, s1))
+        s0 = s1
+    return chunks
+
+
+def chunk_stats(off, cap):
+    """-> (chunks, max_chunk_elems, most sequences in a chunk) of greedy_chunks."""
+    ch = greedy_chunks(off, cap)
+    return len(ch), max(int(off[s1] - off[s0]) for s0, s1 in ch), max(s1 - s0 for s0, s1 in ch)
+
+
+def pair_steps(off):
+    """L - 1 of every pair of sequences the N <= 64 backward kernel walks side by side: the
+    sequences longest first (stable), two at a time, L the longer of the two (an odd count
+    leaves the last one alone).  The kernel stages two steps per matrix-core update, so a pair
+    with L - 1 odd ends in a flush of a half-filled stage."""
+    lengths = np.diff(np.asarray(off, np.int64))
+    srt = lengths[np.argsort(-lengths, kind="stable")]
+    return [int(srt[k]) - 1 for k in range(0, len(srt), 2)]
+
+
+def flush_then_full_stage(off, nwaves):
+    """Whether some wave of `nwaves` (wave w walks pairs w, w + nwaves, ...) meets a pair with
+    L - 1 odd and right after it a pair with L - 1 even and at least 2: the flush arm between
+    two pairs of one wave, then a full stage that a leftover row would corrupt."""
+    st = pair_steps(off)
+    return any(st[p] % 2 == 1 and st[p + nwaves] % 2 == 0 and st[p + nwaves] >= 2
+               for p in range(len(st) - nwaves))
 
 
 @functools.lru_cache(maxsize=None)

@@ -241,7 +241,7 @@ def test_gpu_train_matches_60_digit_golden(gpu, name):
     z = load_golden(name)
     for it in (1, 2):
         got = cv.fit_train(z["pi"], z["a"], z["b"], z["offsets"], z["obs"], z["tags"], max_iter=it, tol=0.0)
-        assert got[3] == it
+        assert got[3] == it and cv.last_fit_stats()["chunks"] == 1
         err, ratio = _golden_err(got[:3], z, it)
         print(f"{name} it={it}: gpu err {err:.3e}, oracle err {float(z['oracle_err'][it - 1]):.3e}, ratio {ratio:.2f}")
         assert err <= 1e-9
@@ -274,7 +274,7 @@ def test_gpu_train_matches_oracle(gpu, n, v, frac, tmax):
     pi0, a0, b0 = _probs(n, v, seed=100 + n)
     iters = 3
     gp, ga, gb, it = cv.fit_train(pi0, a0, b0, off, obs, tags, max_iter=iters, tol=0.0)
-    assert it == iters
+    assert it == iters and cv.last_fit_stats()["chunks"] == 1
     rp, ra, rb, rit = FO.train(pi0, a0, b0, off, obs, tags, iters, 0.0)
     assert rit == iters
     assert_params_match((gp, ga, gb), (rp, ra, rb), atol=1e-9)
@@ -305,7 +305,7 @@ def test_gpu_train_groups_match_oracle(gpu, n, nseq, tmax, frac):
     pi0, a0, b0 = _probs(n, v, seed=500 + n)
     iters = 2
     gp, ga, gb, it = cv.fit_train(pi0, a0, b0, off, obs, tags, max_iter=iters, tol=0.0)
-    assert it == iters
+    assert it == iters and cv.last_fit_stats()["chunks"] == 1
     rp, ra, rb, _ = FO.train(pi0, a0, b0, off, obs, tags, iters, 0.0)
     assert_params_match((gp, ga, gb), (rp, ra, rb), atol=1e-9)
 
@@ -371,6 +371,8 @@ def test_gpu_train_global_scratch_match_oracle(gpu, monkeypatch, n, nseq, tmax, 
     pi0, a0, b0 = _probs(n, v, seed=700 + n)
     gp, ga, gb, it = cv.fit_train(pi0, a0, b0, off, obs, tags, max_iter=2, tol=0.0)
     assert it == 2
+    st = cv.last_fit_stats()  # one chunk; kBwScratchSeqs = 2,048 sequences per global-scratch launch
+    assert (st["chunks"], st["family"], st["scratch_batches"]) == (1, "strided_global", -(-nseq // 2048)), st
     rp, ra, rb, _ = FO.train(pi0, a0, b0, off, obs, tags, 2, 0.0)
     assert_params_match((gp, ga, gb), (rp, ra, rb), atol=1e-9)
 

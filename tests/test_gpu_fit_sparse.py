@@ -38,6 +38,8 @@ def _run(monkeypatch, keys, inputs, iters):
         monkeypatch.setenv(k, "1")
     gp, ga, gb, it = cv.fit_train(*inputs, max_iter=iters, tol=0.0)
     assert it == iters
+    st = cv.last_fit_stats()  # unhooked: one chunk, one pair per wave (tests/test_gpu_fit_chunks.py: several)
+    assert st["chunks"] == 1 and st["pairs_per_wave_max"] <= 1, st
     return gp, ga, gb
 
 

@@ -52,7 +52,9 @@ def test_defaults_and_unknown_keys(monkeypatch):
         monkeypatch.delenv("CV_" + k.upper(), raising=False)
     h = _hmm()
     want = {"t64_s": 0, "t64_wg": 1, "t64_bal": 8, "t64_512": -1, "chain_par": 1, "chain_cert_fused": 1,
-            "generic_rows": 1, "max_chunks": 8, "no_trace": 0, "trace": 0}
+            "generic_rows": 1, "max_chunks": 8, "no_trace": 0, "trace": 0,
+            # the fitting hooks: 0 = the device-memory chunk rule and 8 waves per compute unit
+            "bw_chunk_elems": 0, "bw_max_waves": 0, "bw_global": 0, "bw_perseq": 0, "bw_gemm_path": 0}
     for k, v in want.items():
         assert h.tuning(k) == v, k
     with pytest.raises(cv.CVError, match="EINVAL"):
@@ -143,6 +145,19 @@ def test_every_key_is_named_by_a_gpu_test():
 
     missing = sorted(k for k in keys if k not in exempt and not named(k))
     assert not missing, f"tuning keys no GPU test names: {missing}"
+
+
+def test_fitting_hooks_are_keys_with_their_own_tolerance():
+    """bw_chunk_elems and bw_max_waves are listed, round-trip through a handle like every key
+    (cv_hmm_fit_train itself reads CV_<KEY> per call), and csrc/tuning.h says of the fitting keys
+    what holds for them: the fitting tolerance, not bit identity."""
+    keys = cv.tuning_keys()
+    assert {"bw_chunk_elems", "bw_max_waves"} <= set(keys)
+    h = _hmm()
+    h.set_tuning(bw_chunk_elems=123, bw_max_waves=3)
+    assert h.tuning("bw_chunk_elems") == 123 and h.tuning("bw_max_waves") == 3
+    text = " ".join(open(os.path.join(CSRC, "tuning.h")).read().split())
+    assert "fitting tolerance" in text and "not bit-identical" in text
 
 
 def test_every_key_documented_in_the_header():
