@@ -273,6 +273,15 @@ struct cv_hmm {
   std::vector<int64_t> fx_idx_host;
   bool fx_pinned = false;
   int64_t fx_last[4] = {0, 0, 0, 0};
+  // certified f32 round-up first pass (tuning key t64_f32ru_first): the shifted, rounded-up f32
+  // tables in the same layouts, the shifts ca [N] and cb [V] in f64 (ru_state as fx_state); the
+  // shifts mu_t and losing candidates r_t per element and E per sequence of the last call.
+  // fx_last_kind: which first pass the last call took (0 none, 1 integer, 2 round-up)
+  int ru_state = -1;
+  DevBuf ru_aimg, ru_pi, ru_et, ru_at, ru_ca, ru_cb;
+  double ru_ks = 0.0;
+  DevBuf ru_mu, ru_r, ru_e;
+  int fx_last_kind = 0;
   DevBuf q_pi0;  // the reversed (suffix) pass: pi = 0 for the N states, -inf padding
   // f32 generic tables
   bool g32_ready = false;
@@ -1921,6 +1930,7 @@ CV_API cv_status cv_hmm_set_tuning(cv_hmm* h, const char* key, int64_t value) {
     h->nonpos_cache = -1;
     h->t64_ready = false;
     h->fx_state = -1;  // ensure_fix_tables reads it too: the fixed-point first pass follows the key
+    h->ru_state = -1;  // and so does ensure_ru_tables
   }
   return CV_OK;
 }
@@ -1948,7 +1958,8 @@ CV_API cv_status cv_hmm_release_workspaces(cv_hmm* h) {
                     &h->chainb.sobs, &h->chainb.spath, &h->chainb.sres, &h->chainb.sinit, &h->chainb.slast,
                     &h->chainb.spsi, &h->ps_rows,
                     &h->ps_order, &h->ps_kshift, &h->st_gamma, &h->kb_bp, &h->kb_last, &h->kb_order, &h->kb_end, &h->st_count,
-                    &h->st_emis, &h->fx_cert, &h->fx_idx, &h->fx_obs2, &h->fx_path2, &h->fx_score2, &h->fx_status2})
+                    &h->st_emis, &h->fx_cert, &h->fx_idx, &h->fx_obs2, &h->fx_path2, &h->fx_score2, &h->fx_status2,
+                    &h->ru_mu, &h->ru_r, &h->ru_e})
     b->release();
   h->fx_cert_pin.release();
   h->sm_pin.release();
@@ -2081,7 +2092,97 @@ static cv_status ensure_fix_tables(cv_hmm* h) {
   return CV_OK;
 }
 
-// The plain row-A0 f64 batch decode through the integer pass.  *done = false: the call is not
+// ---- certified f32 round-up first pass (tuning key t64_f32ru_first) ------------------------
+// The smallest float >= x + y, the real sum: the two-sum gives the f64 add's exact remainder.
+// (tools/probe_f32ru.py ru_sum64; the tables hold no +inf and no NaN)
+static float ru_sum32(double x, double y) {
+  const double s = x + y;
+  if (!std::isfinite(s)) return (float)s;
+  const double bb = s - x;
+  const double e = (x - (s - bb)) + (y - bb);
+  float f = (float)s;
+  if ((double)f < s || ((double)f == s && e > 0.0)) f = std::nextafter(f, std::numeric_limits<float>::infinity());
+  return f;
+}
+static double ru_grid(double x) {  // a multiple of 2^-16 near x; a maximum of -inf alone -> 0
+  return std::isfinite(x) ? std::nearbyint(x * 65536.0) / 65536.0 : 0.0;
+}
+
+// The shifted f32 tables, once per handle (DESIGN.md "Certified f32 round-up first pass"):
+// ca_j = grid(max_i a[i,j]), a' = RU(a - ca_j), cb_o = grid(max_j (b[j,o] + ca_j)),
+// b'' = RU(b + (ca_j - cb_o)), pi' = RU(pi - ca_j).  ru_state = 0: outside the pass's range.
+static cv_status ensure_ru_tables(cv_hmm* h) {
+  if (h->ru_state >= 0) return CV_OK;
+  const int np = cvk::trellis_padded_states(h->N);
+  if (!cvk::fix_supported(np) || !model_nonpos(h)) {
+    h->ru_state = 0;
+    return CV_OK;
+  }
+  const int N = h->N;
+  const int64_t V = h->V;
+  const int R = np / 8;
+  const float ninf = -std::numeric_limits<float>::infinity();
+  std::vector<double> ca((size_t)N), cb((size_t)V);
+  for (int j = 0; j < N; ++j) {
+    double m = -INFINITY;
+    for (int i = 0; i < N; ++i) m = std::max(m, h->a[(size_t)i * N + j]);
+    ca[(size_t)j] = ru_grid(m);
+  }
+  for (int64_t o = 0; o < V; ++o) {
+    double m = -INFINITY;
+    for (int j = 0; j < N; ++j) m = std::max(m, h->b[(size_t)j * V + o] + ca[(size_t)j]);
+    cb[(size_t)o] = ru_grid(m);
+  }
+  double smax = 0.0;
+  for (double x : ca) smax = std::max(smax, std::fabs(x));
+  for (double x : cb) smax = std::max(smax, std::fabs(x));
+  if (!(smax < 1073741824.0)) {  // ca - cb would not be exact on the grid
+    h->ru_state = 0;
+    return CV_OK;
+  }
+  auto A = [&](int i, int j) -> float {
+    return (i < N && j < N) ? ru_sum32(h->a[(size_t)i * N + j], -ca[(size_t)j]) : ninf;
+  };
+  std::vector<float> img((size_t)np * np), pi((size_t)np, ninf), at((size_t)np * np, ninf), et((size_t)V * np, ninf);
+  for (int w = 0; w < np / 16; ++w)  // the register image of ensure_trellis_tables
+    for (int q = 0; q < R / 2; ++q)
+      for (int lane = 0; lane < 64; ++lane) {
+        const int rg = lane & 7, cp = lane >> 3, j0 = 16 * w + 2 * cp, r0 = rg * R + 2 * q;
+        float* dst = &img[(((size_t)w * (R / 2) + q) * 64 + lane) * 4];
+        dst[0] = A(r0, j0);
+        dst[1] = A(r0, j0 + 1);
+        dst[2] = A(r0 + 1, j0);
+        dst[3] = A(r0 + 1, j0 + 1);
+      }
+  for (int j = 0; j < N; ++j) pi[(size_t)j] = ru_sum32(h->pi[(size_t)j], -ca[(size_t)j]);
+  for (int i = 0; i < N; ++i)
+    for (int j = 0; j < N; ++j) at[(size_t)j * np + i] = A(i, j);
+  parallel_ranges(N, [&](int, int64_t lo, int64_t hi) {
+    for (int64_t j = lo; j < hi; ++j)
+      for (int64_t o = 0; o < V; ++o)
+        et[(size_t)o * np + j] = ru_sum32(h->b[(size_t)j * V + o], ca[(size_t)j] - cb[(size_t)o]);
+  }, std::max<int64_t>(1, 4096 / std::max<int64_t>(V, 1)));
+  double wmax = 0.0;  // W of ensure_fix_tables
+  for (const std::vector<double>* v : {&h->pi, &h->a, &h->b}) {
+    double m = 0.0;
+    for (double x : *v)
+      if (std::isfinite(x)) m = std::max(m, std::fabs(x));
+    wmax += m;
+  }
+  h->ru_ks = 4.0 * std::ldexp(1.0, -53) * wmax;
+  cv_status st;
+  if ((st = upload(h->ru_aimg, img.data(), img.size() * 4)) != CV_OK) return st;
+  if ((st = upload(h->ru_pi, pi.data(), pi.size() * 4)) != CV_OK) return st;
+  if ((st = upload(h->ru_at, at.data(), at.size() * 4)) != CV_OK) return st;
+  if ((st = upload(h->ru_et, et.data(), et.size() * 4)) != CV_OK) return st;
+  if ((st = upload(h->ru_ca, ca.data(), ca.size() * 8)) != CV_OK) return st;
+  if ((st = upload(h->ru_cb, cb.data(), cb.size() * 8)) != CV_OK) return st;
+  h->ru_state = 1;
+  return CV_OK;
+}
+
+// The plain row-A0 f64 batch decode through a certified first pass, the integer or the f32
+// round-up one by the call's size and the two keys.  *done = false: the call is not
 // the pass's (options, model, batch size, the handle's guard) and nothing has been written; the
 // caller runs the f64 kernels.  Otherwise every sequence has its result: the certified ones from
 // the integer rows (path) and the f64 fold along it (score), the others -- uncertified, unpaired,
@@ -2093,17 +2194,31 @@ static cv_status fixed_first_decode(cv_hmm* h, int64_t nseq, const int64_t* offs
   *done = false;
   h->fx_last[0] = h->fx_last[1] = h->fx_last[2] = 0;
   h->fx_last[3] = h->fx_pinned ? 1 : 0;
-  const int64_t min_elems = h->tuning.t64_fixed_first;
-  if (min_elems <= 0 || h->fx_pinned || h->fx_state == 0 || nseq < 2 || nseq > INT32_MAX) return CV_OK;
+  h->fx_last_kind = 0;
+  // the pass is a parameter of everything below: kRu (the f32 round-up pass) for a call of at least
+  // t64_f32ru_first elements, kFix (the integer pass) for one below that and at least t64_fixed_first
+  enum FirstPass { kNone = 0, kFix = 1, kRu = 2 };
+  const int64_t min_fix = h->tuning.t64_fixed_first, min_ru = h->tuning.t64_f32ru_first;
+  const bool fix_open = min_fix > 0 && h->fx_state != 0, ru_open = min_ru > 0 && h->ru_state != 0;
+  if ((!fix_open && !ru_open) || h->fx_pinned || nseq < 2 || nseq > INT32_MAX) return CV_OK;
   if (o.dtype != CV_DTYPE_F64 || o.assoc != CV_ASSOC_VITERBI || o.forced || o.flags != 0 ||
       (o.kernel != CV_KERNEL_AUTO && o.kernel != CV_KERNEL_TRELLIS_F64))
     return CV_OK;
   std::vector<int64_t> off_copy;
   cv_status st = host_offsets(nseq, offsets_host, offsets_dev, off_copy, stream);
   if (st != CV_OK) return st;
-  if (offsets_host[nseq] - offsets_host[0] < min_elems) return CV_OK;
-  if ((st = ensure_fix_tables(h)) != CV_OK) return st;
-  if (h->fx_state != 1) return CV_OK;
+  const int64_t elems = offsets_host[nseq] - offsets_host[0];
+  FirstPass pass = kNone;
+  if (ru_open && elems >= min_ru) {
+    if ((st = ensure_ru_tables(h)) != CV_OK) return st;
+    if (h->ru_state == 1) pass = kRu;
+  }
+  if (pass == kNone && fix_open && elems >= min_fix) {
+    if ((st = ensure_fix_tables(h)) != CV_OK) return st;
+    if (h->fx_state == 1) pass = kFix;
+  }
+  if (pass == kNone) return CV_OK;
+  const bool ru = pass == kRu;
   if ((st = ensure_f64_tables(h)) != CV_OK) return st;
   const int np = cvk::trellis_padded_states(h->N);
 
@@ -2137,6 +2252,12 @@ static cv_status fixed_first_decode(cv_hmm* h, int64_t nseq, const int64_t* offs
     h->order_host.resize((size_t)nseq);
     cvplan::longest_first(offsets_host, chunks, h->order_host.data(), npair.data(), h->sort_pos);
     if ((st = upload_order(h->ws_order, h->order_pin, h->order_host.data(), nseq, stream, &order_dev)) != CV_OK) return st;
+  }
+  if (ru) {  // the shifts and losing candidates, by element like the path; E by sequence
+    const size_t ne = (size_t)std::max<int64_t>(offsets_host[nseq], 1);
+    if ((st = h->ru_mu.ensure(ne * 4)) != CV_OK) return st;
+    if ((st = h->ru_r.ensure(ne * 4)) != CV_OK) return st;
+    if ((st = h->ru_e.ensure((size_t)nseq * 4)) != CV_OK) return st;
   }
   HIP_TRY(hipMemsetAsync(h->fx_cert.p, 0, (size_t)nseq, stream));
 
@@ -2173,20 +2294,41 @@ static cv_status fixed_first_decode(cv_hmm* h, int64_t nseq, const int64_t* offs
     hipEvent_t f0 = e4[0], f1 = e4[1], b0 = e4[2], b1 = e4[3];
     if (!serial && ci >= 2) HIP_TRY(hipStreamWaitEvent(stream, h->ev[eb + 4 * (ci - 2) + 3], 0));  // buffer reuse
     HIP_TRY(hipEventRecord(f0, stream));
-    cvk::FixFwdArgs fa{};
-    fa.a_img = h->fx_aimg.as<int32_t>();
-    fa.pi = h->fx_pi.as<int32_t>();
-    fa.et = h->fx_et.as<int32_t>();
-    fa.offsets = offsets_dev;
-    fa.obs = obs_dev;
-    fa.order = order_dev;
-    fa.seq_begin = c.first;
-    fa.rows = reinterpret_cast<int32_t*>(h->ws_main.as<unsigned char>() + (nbuf == 2 ? ci % 2 : 0) * buf_bytes);
-    fa.row_elem_base = offsets_host[c.first];
-    fa.cert = h->fx_cert.as<uint8_t>();
-    fa.nobs = (int)h->V;
-    hipError_t err = cvk::launch_fix_fwd2(np, fa, np2, stream);
-    if (err != hipSuccess) return set_err(CV_EDEVICE, "fixed-point forward launch failed: %s", hipGetErrorString(err));
+    void* const rows = h->ws_main.as<unsigned char>() + (nbuf == 2 ? ci % 2 : 0) * buf_bytes;
+    const int64_t row_base = offsets_host[c.first];
+    uint8_t* const cert_dev = h->fx_cert.as<uint8_t>();
+    hipError_t err;
+    if (ru) {
+      cvk::RuFwdArgs fa{};
+      fa.a_img = h->ru_aimg.as<float>();
+      fa.pi = h->ru_pi.as<float>();
+      fa.et = h->ru_et.as<float>();
+      fa.offsets = offsets_dev;
+      fa.obs = obs_dev;
+      fa.order = order_dev;
+      fa.seq_begin = c.first;
+      fa.rows = static_cast<float*>(rows);
+      fa.row_elem_base = row_base;
+      fa.mu = h->ru_mu.as<float>();
+      fa.cert = cert_dev;
+      fa.nobs = (int)h->V;
+      err = cvk::launch_ru_fwd2(np, fa, np2, stream);
+    } else {
+      cvk::FixFwdArgs fa{};
+      fa.a_img = h->fx_aimg.as<int32_t>();
+      fa.pi = h->fx_pi.as<int32_t>();
+      fa.et = h->fx_et.as<int32_t>();
+      fa.offsets = offsets_dev;
+      fa.obs = obs_dev;
+      fa.order = order_dev;
+      fa.seq_begin = c.first;
+      fa.rows = static_cast<int32_t*>(rows);
+      fa.row_elem_base = row_base;
+      fa.cert = cert_dev;
+      fa.nobs = (int)h->V;
+      err = cvk::launch_fix_fwd2(np, fa, np2, stream);
+    }
+    if (err != hipSuccess) return set_err(CV_EDEVICE, "first-pass forward launch failed: %s", hipGetErrorString(err));
     HIP_TRY(hipEventRecord(f1, stream));
     if (!serial) {
       HIP_TRY(hipStreamWaitEvent(bts, f1, 0));
@@ -2196,33 +2338,71 @@ static cv_status fixed_first_decode(cv_hmm* h, int64_t nseq, const int64_t* offs
     // beside the next chunk's forward: one backtrack / score workgroup per CU (launch_fix_bt); the
     // last chunk's have the device to themselves
     const int reserve = (serial || ci + 1 == chunks.size()) ? 0 : 100 * 1024;
-    cvk::FixBtArgs ba{};
-    ba.rows = fa.rows;
-    ba.row_elem_base = fa.row_elem_base;
-    ba.at = h->fx_at.as<int32_t>();
-    ba.offsets = offsets_dev;
-    ba.order = order_dev;
-    ba.seq_begin = c.first;
-    ba.seq_end = c.first + 2 * np2;  // the paired slots: only their rows exist
-    ba.gain = h->fx_gain;
-    ba.path = path_dev;
-    ba.cert = fa.cert;
-    err = cvk::launch_fix_bt(np, ba, bts, reserve);
-    if (err == hipSuccess) {
-      cvk::FixScoreArgs ra{};
-      ra.path = path_dev;
-      ra.obs = obs_dev;
-      ra.offsets = offsets_dev;
-      ra.seq_begin = c.first;
-      ra.seq_end = c.second;
-      ra.nstates = h->N;
-      ra.pi64 = h->d_pi64.as<double>();
-      ra.a64 = h->d_a64.as<double>();
-      ra.et64 = h->d_et64.as<double>();
-      ra.cert = fa.cert;
-      ra.score = score_dev;
-      ra.status = status_dev;
-      err = cvk::launch_fix_score(ra, bts, reserve);
+    if (ru) {
+      cvk::RuBtArgs ba{};
+      ba.rows = static_cast<const float*>(rows);
+      ba.row_elem_base = row_base;
+      ba.at = h->ru_at.as<float>();
+      ba.offsets = offsets_dev;
+      ba.order = order_dev;
+      ba.seq_begin = c.first;
+      ba.seq_end = c.first + 2 * np2;  // the paired slots: only their rows exist
+      ba.path = path_dev;
+      ba.r = h->ru_r.as<float>();
+      ba.e_last = h->ru_e.as<float>();
+      ba.cert = cert_dev;
+      err = cvk::launch_ru_bt(np, ba, bts, reserve);
+      if (err == hipSuccess) {
+        cvk::RuScoreArgs ra{};
+        ra.path = path_dev;
+        ra.obs = obs_dev;
+        ra.offsets = offsets_dev;
+        ra.seq_begin = c.first;
+        ra.seq_end = c.second;
+        ra.nstates = h->N;
+        ra.pi64 = h->d_pi64.as<double>();
+        ra.a64 = h->d_a64.as<double>();
+        ra.et64 = h->d_et64.as<double>();
+        ra.ca = h->ru_ca.as<double>();
+        ra.cb = h->ru_cb.as<double>();
+        ra.mu = h->ru_mu.as<float>();
+        ra.r = h->ru_r.as<float>();
+        ra.e_last = h->ru_e.as<float>();
+        ra.ks = h->ru_ks;
+        ra.cert = cert_dev;
+        ra.score = score_dev;
+        ra.status = status_dev;
+        err = cvk::launch_ru_score(ra, bts, reserve);
+      }
+    } else {
+      cvk::FixBtArgs ba{};
+      ba.rows = static_cast<const int32_t*>(rows);
+      ba.row_elem_base = row_base;
+      ba.at = h->fx_at.as<int32_t>();
+      ba.offsets = offsets_dev;
+      ba.order = order_dev;
+      ba.seq_begin = c.first;
+      ba.seq_end = c.first + 2 * np2;  // the paired slots: only their rows exist
+      ba.gain = h->fx_gain;
+      ba.path = path_dev;
+      ba.cert = cert_dev;
+      err = cvk::launch_fix_bt(np, ba, bts, reserve);
+      if (err == hipSuccess) {
+        cvk::FixScoreArgs ra{};
+        ra.path = path_dev;
+        ra.obs = obs_dev;
+        ra.offsets = offsets_dev;
+        ra.seq_begin = c.first;
+        ra.seq_end = c.second;
+        ra.nstates = h->N;
+        ra.pi64 = h->d_pi64.as<double>();
+        ra.a64 = h->d_a64.as<double>();
+        ra.et64 = h->d_et64.as<double>();
+        ra.cert = cert_dev;
+        ra.score = score_dev;
+        ra.status = status_dev;
+        err = cvk::launch_fix_score(ra, bts, reserve);
+      }
     }
     if (err != hipSuccess) return set_err(CV_EDEVICE, "fixed-point backtrack launch failed: %s", hipGetErrorString(err));
     HIP_TRY(hipEventRecord(b1, bts));
@@ -2241,6 +2421,7 @@ static cv_status fixed_first_decode(cv_hmm* h, int64_t nseq, const int64_t* offs
   int64_t nfb = 0, nfail = 0;  // not certified; of them, the pass ran to a failed certificate (2)
   for (int64_t s = 0; s < nseq; ++s) nfb += cert[s] != 1, nfail += cert[s] == 2;
   h->fx_last[0] = 1;
+  h->fx_last_kind = (int)pass;
   h->fx_last[1] = nseq - nfb;
   h->fx_last[2] = nfb;
   h->fx_last[3] = 0;
@@ -4036,6 +4217,80 @@ CV_API int32_t cv_last_fixed_first_stats(const cv_hmm* h, int64_t* out, int32_t 
   }
   for (int32_t q = 0; q < n && q < 4; ++q) out[q] = h->fx_last[q];
   return 4;
+}
+
+CV_API int32_t cv_last_first_pass_kind(const cv_hmm* h) {
+  if (!h) {
+    set_err(CV_EINVAL, "null handle");
+    return -1;
+  }
+  return h->fx_last_kind;
+}
+
+// The round-up pass's forward and certificate backtrack on nseq sequences of one length T,
+// everything they store copied out: what tests compare with the numpy model bit for bit.
+CV_API cv_status cv_f32ru_trace(cv_hmm* h, int64_t nseq, int64_t T, const int32_t* obs, float* rows, float* mu,
+                                float* r, float* e_last, int32_t* path) {
+  if (!h || !obs || !rows || !mu || !r || !e_last || !path) return set_err(CV_EINVAL, "null argument");
+  if (nseq < 2 || T < 1 || nseq * T > (1 << 22)) return set_err(CV_EINVAL, "bad batch shape");
+  CV_LOCK(h);
+  cv_status st = set_device(h);
+  if (st != CV_OK) return st;
+  for (int64_t e = 0; e < nseq * T; ++e)
+    if (obs[e] < 0 || obs[e] >= h->V) return set_err(CV_EINVAL, "observation out of range");
+  if ((st = ensure_ru_tables(h)) != CV_OK) return st;
+  if (h->ru_state != 1) return set_err(CV_EINVAL, "the model is outside the round-up pass's range");
+  const int np = cvk::trellis_padded_states(h->N);
+  const size_t ne = (size_t)(nseq * T);
+  std::vector<int64_t> off((size_t)nseq + 1);
+  for (int64_t s = 0; s <= nseq; ++s) off[(size_t)s] = s * T;
+  DevBuf d_off, d_obs, d_rows, d_mu, d_r, d_e, d_path, d_cert;
+  if ((st = upload(d_off, off.data(), off.size() * 8)) != CV_OK) return st;
+  if ((st = upload(d_obs, obs, ne * 4)) != CV_OK) return st;
+  if ((st = d_rows.ensure(ne * np * 4)) != CV_OK) return st;
+  if ((st = d_mu.ensure(ne * 4)) != CV_OK) return st;
+  if ((st = d_r.ensure(ne * 4)) != CV_OK) return st;
+  if ((st = d_e.ensure((size_t)nseq * 4)) != CV_OK) return st;
+  if ((st = d_path.ensure(ne * 4)) != CV_OK) return st;
+  if ((st = d_cert.ensure((size_t)nseq)) != CV_OK) return st;
+  hipStream_t stream = h->stream;
+  HIP_TRY(hipMemsetAsync(d_cert.p, 0, (size_t)nseq, stream));
+  HIP_TRY(hipMemsetAsync(d_mu.p, 0, ne * 4, stream));
+  HIP_TRY(hipMemsetAsync(d_r.p, 0, ne * 4, stream));
+  HIP_TRY(hipMemsetAsync(d_rows.p, 0, ne * np * 4, stream));  // an odd count leaves its last sequence alone
+  HIP_TRY(hipMemsetAsync(d_path.p, 0, ne * 4, stream));
+  HIP_TRY(hipMemsetAsync(d_e.p, 0, (size_t)nseq * 4, stream));
+  cvk::RuFwdArgs fa{};
+  fa.a_img = h->ru_aimg.as<float>();
+  fa.pi = h->ru_pi.as<float>();
+  fa.et = h->ru_et.as<float>();
+  fa.offsets = d_off.as<int64_t>();
+  fa.obs = d_obs.as<int32_t>();
+  fa.rows = d_rows.as<float>();
+  fa.mu = d_mu.as<float>();
+  fa.cert = d_cert.as<uint8_t>();
+  fa.nobs = (int)h->V;
+  hipError_t err = cvk::launch_ru_fwd2(np, fa, nseq / 2, stream);
+  cvk::RuBtArgs ba{};
+  ba.rows = fa.rows;
+  ba.at = h->ru_at.as<float>();
+  ba.offsets = fa.offsets;
+  ba.seq_end = nseq - (nseq & 1);
+  ba.path = d_path.as<int32_t>();
+  ba.r = d_r.as<float>();
+  ba.e_last = d_e.as<float>();
+  ba.cert = fa.cert;
+  if (err == hipSuccess) err = cvk::launch_ru_bt(np, ba, stream, 0);
+  if (err != hipSuccess) return set_err(CV_EDEVICE, "round-up pass launch failed: %s", hipGetErrorString(err));
+  HIP_TRY(hipStreamSynchronize(stream));
+  std::vector<float> padded(ne * (size_t)np);
+  HIP_TRY(hipMemcpy(padded.data(), d_rows.p, padded.size() * 4, hipMemcpyDeviceToHost));
+  for (size_t e = 0; e < ne; ++e) std::memcpy(rows + e * (size_t)h->N, &padded[e * (size_t)np], (size_t)h->N * 4);
+  HIP_TRY(hipMemcpy(mu, d_mu.p, ne * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(r, d_r.p, ne * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(e_last, d_e.p, (size_t)nseq * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(path, d_path.p, ne * 4, hipMemcpyDeviceToHost));
+  return CV_OK;
 }
 
 CV_API cv_status cv_last_suffix_traced(const cv_hmm* h, int64_t* out) {

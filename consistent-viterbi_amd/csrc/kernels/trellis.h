@@ -124,6 +124,59 @@ hipError_t launch_fix_fwd2(int np, const FixFwdArgs& fa, int64_t npairs, hipStre
 hipError_t launch_fix_bt(int np, const FixBtArgs& ba, hipStream_t stream, int lds_reserve = 0);
 hipError_t launch_fix_score(const FixScoreArgs& r, hipStream_t stream, int lds_reserve = 0);
 
+// Certified f32 round-up first pass (trellis_fwd2_f32ru, backtrack_f32ru, ru_score_f64; DESIGN.md
+// "Certified f32 round-up first pass"): f32 tables shifted per column (ca) and per observation (cb)
+// and rounded toward +inf, in the layouts of the f32 trellis tables; the rows share the integer
+// pass's workspace.  mu and r are indexed by element like the path, e_last by sequence.
+struct RuFwdArgs {
+  const float* a_img;
+  const float* pi;
+  const float* et;
+  const int64_t* offsets;
+  const int32_t* obs;
+  const int32_t* order;    // optional schedule: slot -> sequence id
+  int64_t seq_begin;       // slots seq_begin + 2k, + 2k + 1 hold a pair of equal length
+  float* rows;             // [(elements of chunk)][NP]
+  int64_t row_elem_base;
+  float* mu;               // [elements]: element t >= 1 of a sequence holds the shift of its row t
+  uint8_t* cert;           // [nseq_total], zeroed: CVK_SEQ_BADOBS where an observation is out of range
+  int nobs;
+};
+struct RuBtArgs {
+  const float* rows;
+  int64_t row_elem_base;
+  const float* at;
+  const int64_t* offsets;
+  const int32_t* order;
+  int64_t seq_begin, seq_end;  // slots
+  int32_t* path;
+  float* r;                // [elements]: element t >= 1 holds the largest losing candidate of step t
+  float* e_last;           // [nseq_total]: the largest entry of the last row beside the winner
+  uint8_t* cert;           // 0 -> 1: the candidate path is written (ru_score_f64 decides)
+};
+struct RuScoreArgs {
+  const int32_t* path;
+  const int32_t* obs;
+  const int64_t* offsets;
+  int64_t seq_begin, seq_end;  // sequences
+  int nstates;
+  const double* pi64;
+  const double* a64;
+  const double* et64;
+  const double* ca;        // [nstates]
+  const double* cb;        // [nobs]
+  const float* mu;
+  const float* r;
+  const float* e_last;
+  double ks;               // 4 u W: the f64 recurrence's rounding per squared step
+  uint8_t* cert;           // 1 -> 2 where the certificate fails
+  double* score;           // written with status OK where cert stays 1
+  uint8_t* status;
+};
+hipError_t launch_ru_fwd2(int np, const RuFwdArgs& fa, int64_t npairs, hipStream_t stream);
+hipError_t launch_ru_bt(int np, const RuBtArgs& ba, hipStream_t stream, int lds_reserve = 0);
+hipError_t launch_ru_score(const RuScoreArgs& r, hipStream_t stream, int lds_reserve = 0);
+
 template <typename REAL>
 struct GenericFwdArgs {
   const int32_t* forced;   // [sum T] nullable: -1 free, else forced state

@@ -1268,6 +1268,347 @@ hipError_t launch_fix_score(const FixScoreArgs& r, hipStream_t stream, int lds_r
 }
 
 // ---------------------------------------------------------------------------------
+// Certified f32 round-up first pass of the exact f64 decode (DESIGN.md "Certified f32 round-up
+// first pass"; tools/probe_f32ru.py is the numpy model these kernels follow bit for bit).  Every
+// f32 add of the forward and the backtrack rounds toward +inf, so every stored value is an upper
+// bound of the real recurrence; the certificate (ru_score_f64) compares the exact f64 fold along
+// the candidate path with those bounds.
+//   trellis_fwd2_f32ru  trellis_fwd2_f32's layout and mix (one v_add_f32 and half a v_max3_f32 per
+//                       pair, one barrier per step) with trellis_fwd2_i32's row shift: row t is
+//                       stored minus mu_t, the maximum of row t-1.
+//   backtrack_f32ru     one wave per sequence: first argmax w and r_t, the largest other candidate,
+//                       at every step, and E beside the terminal winner.
+//   ru_score_f64        one lane per sequence, default rounding: the f64 fold and the certificate.
+// The waves of the first two set the single-precision round field of their MODE register
+// (bits 1:0) to 1, toward +inf, before any f32 operand is loaded; the register is per wave and
+// initialised from the kernel descriptor at launch, so no other kernel sees it.  Denormal and f64
+// fields keep their values.
+__device__ __forceinline__ void round_f32_up() {
+  // hwreg(HW_REG_MODE, offset 0, width 2) = id 1 | 0 << 6 | (2 - 1) << 11
+  __builtin_amdgcn_s_setreg(1 | (1 << 11), 1);
+  asm volatile("" ::: "memory");  // the loads that feed the adds stay behind the mode change
+}
+__device__ __forceinline__ float dpp_max_half_mirror(float x) {
+  asm volatile("s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf" : "+v"(x));
+  return x;
+}
+
+template <int NP>
+__global__ __launch_bounds__(NP * 4) void trellis_fwd2_f32ru(RuFwdArgs args) {
+  using G = TrellisGeom<NP>;
+  constexpr int R = G::R;
+  constexpr int S = G::S;
+  static_assert(R % 8 == 0, "pair kernel needs NP % 64 == 0");
+  __shared__ __attribute__((aligned(16))) float lds[2][2][G::LDS_FLOATS];  // [X/Y][buffer]
+  __shared__ float mu[2][3];  // [X/Y][t % 3]: the maximum of row t
+  round_f32_up();
+
+  const int lane = threadIdx.x & 63;
+  const int w = threadIdx.x >> 6;
+  const int rg = lane & 7;
+  const int cp = lane >> 3;
+  const int j0 = 16 * w + 2 * cp;
+  const bool hi = rg >= 4;  // column of this lane after the fold: j0 + hi
+  const unsigned jw = (unsigned)(j0 + (hi ? 1 : 0));
+
+  const int64_t slot = args.seq_begin + 2 * (int64_t)blockIdx.x;
+  const int64_t seqX = args.order ? (int64_t)args.order[slot] : slot;
+  const int64_t seqY = args.order ? (int64_t)args.order[slot + 1] : slot + 1;
+  const int64_t eX = args.offsets[seqX], eY = args.offsets[seqY];
+  const int T = (int)(args.offsets[seqX + 1] - eX);  // the host pairs equal lengths
+  if (T <= 0) return;
+  typedef const __attribute__((address_space(4))) int32_t* cobs_t;
+  const cobs_t obsX = (cobs_t)(args.obs + eX);
+  const cobs_t obsY = (cobs_t)(args.obs + eY);
+  float* const dX = args.rows + (eX - args.row_elem_base) * NP;  // uniform row bases
+  float* const dY = args.rows + (eY - args.row_elem_base) * NP;
+  float* const muX = args.mu + eX;
+  float* const muY = args.mu + eY;
+  const unsigned V = (unsigned)args.nobs;
+
+  if (threadIdx.x < 6) (&mu[0][0])[threadIdx.x] = ninf_f();
+  __builtin_amdgcn_s_setprio(3);  // as trellis_fwd2_f32: the forward wins issue over a co-resident backtrack
+  float a_reg[2 * R];
+  {
+    const float4* img = reinterpret_cast<const float4*>(args.a_img) + (size_t)w * (R / 2) * 64 + lane;
+#pragma unroll
+    for (int q = 0; q < R / 2; ++q) {
+      const float4 v = img[q * 64];
+      a_reg[4 * q + 0] = v.x;
+      a_reg[4 * q + 1] = v.y;
+      a_reg[4 * q + 2] = v.z;
+      a_reg[4 * q + 3] = v.w;
+    }
+  }
+  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the A image is resident before the step loop
+  unsigned bad = 0;                    // bit 0: X, bit 1: Y
+  auto obs_x = [&](int t) -> unsigned {
+    const unsigned o = (unsigned)obsX[t];
+    bad |= (o >= V) ? 1u : 0u;
+    return o < V ? o : 0u;
+  };
+  auto obs_y = [&](int t) -> unsigned {
+    const unsigned o = (unsigned)obsY[t];
+    bad |= (o >= V) ? 2u : 0u;
+    return o < V ? o : 0u;
+  };
+  auto et_row = [&](unsigned o) -> float { return (args.et + (size_t)o * NP)[jw]; };
+  const int lds_w = (j0 / R) * S + (j0 % R) + (hi ? 1 : 0);
+  auto clampT = [&](int t) { return t < T ? t : T - 1; };
+  // the row maximum as in trellis_fwd2_i32: one DPP level folds an octet's two columns, one lane
+  // per octet posts it with an LDS float atomic max (inline asm: no atomic-optimiser prologue;
+  // lds_barrier waits for lgkmcnt(0) before the barrier that publishes it)
+  typedef __attribute__((address_space(3))) float* lds_float_t;
+  auto post_max = [&](float v, float* dst) {
+    const float m = dpp_max_half_mirror(v);
+    if (rg == 0) asm volatile("ds_max_f32 %0, %1" : : "v"((unsigned)(size_t)(lds_float_t)dst), "v"(m) : "memory");
+  };
+  lds_barrier();  // mu initialised
+
+  float eXr;  // X at t = 1
+  {           // t = 0 for both sequences
+    const float ex = et_row(obs_x(0)), ey = et_row(obs_y(0));
+    const float p = args.pi[jw];
+    // loaded BEFORE the two row stores: the first step then finds the vector-memory queue as every
+    // later one does (emission load, two stores, the next emission load), so the loop's wait for
+    // its emission row is vmcnt(3) on both paths into the loop header and never drains the stores
+    eXr = et_row(obs_x(clampT(1)));
+    const float dx = p + ex, dy = p + ey;
+    lds[0][0][lds_w] = dx;
+    lds[1][0][lds_w] = dy;
+    dX[jw] = dx;
+    dY[jw] = dy;
+    post_max(dx, &mu[0][0]);
+    post_max(dy, &mu[1][0]);
+  }
+  float eYr;
+  unsigned oY = obs_y(clampT(1));
+  unsigned oX = obs_x(clampT(2));
+  lds_barrier();
+  constexpr int KB = R / 8;  // 8-row blocks per lane
+  auto ld8 = [&](const float* src, float4 (&dst)[2]) {
+    dst[0] = *reinterpret_cast<const float4*>(src);
+    dst[1] = *reinterpret_cast<const float4*>(src + 4);
+  };
+  float4 P[2], Q[2];
+  ld8(&lds[0][0][rg * S], P);
+
+  // One half-step at step t (trellis_fwd2_f32's ONEBAR form: the barrier follows the X half).
+  // mus = this sequence's mu slots, mrow = its shifts in memory.
+  auto half = [&](const float* dsrc, const float* nsrc, float* ldst, float* drow, float* mus, float* mrow, int t,
+                  const float& e_use, float& e_load, unsigned& o_load, bool first, int t_obs) {
+    e_load = et_row(o_load);
+    // the maximum of row t-1; a row of -inf alone (an infeasible prefix) shifts by -FLT_MAX, which
+    // keeps it -inf without a NaN
+    const float mu_use = fmaxf(mus[(t + 2) % 3], -__FLT_MAX__);
+    if (threadIdx.x == 0) mus[(t + 1) % 3] = ninf_f();
+    if (KB > 1) ld8(dsrc + 8, Q);
+    float m0a = ninf_f(), m0b = ninf_f(), m1a = ninf_f(), m1b = ninf_f();
+    auto rows4 = [&](const float4& dd, int k, bool init) {
+      const float s00 = dd.x + a_reg[2 * k + 0], s01 = dd.x + a_reg[2 * k + 1];
+      const float s10 = dd.y + a_reg[2 * k + 2], s11 = dd.y + a_reg[2 * k + 3];
+      const float s20 = dd.z + a_reg[2 * k + 4], s21 = dd.z + a_reg[2 * k + 5];
+      const float s30 = dd.w + a_reg[2 * k + 6], s31 = dd.w + a_reg[2 * k + 7];
+      if (init) {
+        m0a = fmaxf(s00, s10);
+        m1a = fmaxf(s01, s11);
+        m0b = fmaxf(s20, s30);
+        m1b = fmaxf(s21, s31);
+      } else {
+        m0a = fmaxf(fmaxf(m0a, s00), s10);
+        m1a = fmaxf(fmaxf(m1a, s01), s11);
+        m0b = fmaxf(fmaxf(m0b, s20), s30);
+        m1b = fmaxf(fmaxf(m1b, s21), s31);
+      }
+    };
+#pragma unroll
+    for (int k = 0; k < KB; ++k) {
+      float4(&B)[2] = (k & 1) ? Q : P;
+      rows4(B[0], 8 * k, k == 0);
+      rows4(B[1], 8 * k + 4, false);
+      __builtin_amdgcn_sched_barrier(0);
+      if (k + 2 < KB)
+        ld8(dsrc + 8 * (k + 2), B);
+      else if (!(k & 1) && (k + 2 == KB || k + 1 == KB) && !first)
+        ld8(nsrc, P);  // next half-step's block 0
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    const float m0 = fmaxf(m0a, m0b);
+    const float m1 = fmaxf(m1a, m1b);
+    float m = dpp_max_mirror(hi ? m1 : m0, hi ? m0 : m1);
+    m = dpp_max_xor1(m);
+    m = dpp_max_xor2(m);
+    const float dn = (m + e_use) - mu_use;  // RU(RU(m + b'') - mu)
+    __builtin_amdgcn_sched_barrier(0);
+    o_load = first ? obs_y(t_obs) : obs_x(t_obs);
+    // every lane stores, as in trellis_fwd2_f32 (a store under a condition is not in the compiler's
+    // vmcnt count); the shift is one dword per sequence and step, the same in every lane
+    ldst[lds_w] = dn;
+    (drow + (size_t)t * NP)[jw] = dn;
+    mrow[t] = mu_use;
+    post_max(dn, &mus[t % 3]);
+    if (first) {
+      lds_barrier();
+      ld8(nsrc, P);  // Y's delta_{t-1}, complete since the barrier
+    }
+  };
+  auto step = [&](int t) {
+    const int cur = (t - 1) & 1, nxt = t & 1;
+    half(&lds[0][cur][rg * S], &lds[1][cur][rg * S], &lds[0][nxt][0], dX, mu[0], muX, t, eXr, eYr, oY, true,
+         clampT(t + 1));
+    half(&lds[1][cur][rg * S], &lds[0][nxt][rg * S], &lds[1][nxt][0], dY, mu[1], muY, t, eYr, eXr, oX, false,
+         clampT(t + 2));
+  };
+  for (int t = 1; t < T; ++t) step(t);
+  if (bad && lane == 0 && w == 0) {
+    if (bad & 1u) args.cert[seqX] = CVK_SEQ_BADOBS;
+    if (bad & 2u) args.cert[seqY] = CVK_SEQ_BADOBS;
+  }
+}
+
+template <int NP>
+__global__ __launch_bounds__(256) void backtrack_f32ru(RuBtArgs args) {
+  constexpr int VL = NP / 64;
+  constexpr int PF = 8;
+  static_assert(VL == 4, "float4 rows");
+  round_f32_up();
+  const int lane = threadIdx.x & 63;
+  const int64_t slot = args.seq_begin + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (slot >= args.seq_end) return;
+  const int64_t seq = args.order ? (int64_t)args.order[slot] : slot;
+  const int64_t e0 = args.offsets[seq];
+  const int T = (int)(args.offsets[seq + 1] - e0);
+  if (T <= 0 || args.cert[seq] != 0) return;  // empty, bad observation: the f64 decode's business
+  int32_t* __restrict__ path = args.path + e0;
+  float* __restrict__ rout = args.r + e0;
+  const float* __restrict__ drow = args.rows + (e0 - args.row_elem_base) * NP + VL * lane;
+  const float* __restrict__ at = args.at + VL * lane;
+  auto load_row = [&](int r, float (&dst)[VL]) {
+    if (r >= 0) {
+      ld_vl<VL>(drow + (size_t)r * NP, dst);
+    } else {
+      dst[0] = dst[1] = dst[2] = dst[3] = ninf_f();
+    }
+  };
+  // first argmax of s, and the largest value at any other index
+  auto top2 = [&](const float (&s)[VL], float& M2) -> int {
+    const float M = wave_max(fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3])));
+    const int win = first_argmax_vl<VL>(s, M, lane) & (NP - 1);  // always a state: it indexes A^T
+    float o = ninf_f();
+#pragma unroll
+    for (int k = 0; k < VL; ++k) o = fmaxf(o, (VL * lane + k == win) ? ninf_f() : s[k]);
+    M2 = wave_max(o);
+    return win;
+  };
+  int cur;
+  float M2;
+  {
+    float last[VL];
+    load_row(T - 1, last);
+    cur = top2(last, M2);
+    if (lane == 0) args.e_last[seq] = M2;
+  }
+  int pathreg = 0;
+  float rreg = 0.0f;
+  if (lane == ((T - 1) & 63)) pathreg = cur;
+  if (((T - 1) & 63) == 0 && lane == 0) path[T - 1] = cur;
+  float ring[PF][VL];
+#pragma unroll
+  for (int u = 0; u < PF; ++u) load_row(T - 2 - u, ring[u]);
+  for (int base = T - 1; base >= 1; base -= PF) {
+#pragma unroll
+    for (int u = 0; u < PF; ++u) {
+      const int t = base - u;
+      if (t >= 1) {
+        float acol[VL];
+        ld_vl<VL>(at + (size_t)cur * NP, acol);
+        const float sv[VL] = {ring[u][0] + acol[0], ring[u][1] + acol[1], ring[u][2] + acol[2], ring[u][3] + acol[3]};
+        cur = top2(sv, M2);
+        // r_t goes out in 64-entry blocks like the path: lane t & 63 holds r_t until t & 63 == 0
+        if (lane == (t & 63)) rreg = M2;
+        if ((t & 63) == 0 && t + lane < T) rout[t + lane] = rreg;
+        const int tp = t - 1;
+        if (lane == (tp & 63)) pathreg = cur;
+        if ((tp & 63) == 0 && tp + lane < T) path[tp + lane] = pathreg;  // flush a 64-entry block
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < PF; ++u) load_row(base - PF - 1 - u, ring[u]);
+  }
+  // the last block of r (elements 1 .. 63; element 0 has no step)
+  if (lane >= 1 && lane < T && lane < 64) rout[lane] = rreg;
+  if (lane == 0) args.cert[seq] = 1;
+}
+
+__global__ __launch_bounds__(64) void ru_score_f64(RuScoreArgs r) {
+  const int64_t seq = r.seq_begin + (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (seq >= r.seq_end || r.cert[seq] != 1) return;
+  const int64_t e0 = r.offsets[seq];
+  const int T = (int)(r.offsets[seq + 1] - e0);
+  const int32_t* __restrict__ path = r.path + e0;
+  const int32_t* __restrict__ obs = r.obs + e0;
+  const float* __restrict__ mu = r.mu + e0;
+  const float* __restrict__ rr = r.r + e0;
+  const int N = r.nstates;
+  auto absfin = [](double x) { return __builtin_isinf(x) ? 0.0 : __builtin_fabs(x); };
+  auto sigma = [&](int n, double s) { return r.ks * (((double)n + 2.0) * ((double)n + 2.0)) + 0x1p-49 * s; };
+  int pp = path[0];
+  double L = r.pi64[pp] + r.et64[(size_t)obs[0] * N + pp];
+  double C = r.cb[obs[0]];
+  bool ok = true;
+  for (int t = 1; t < T; ++t) {
+    const int p = path[t];
+    const int o = obs[t];
+    const double rt = (double)rr[t], cap = r.ca[p];
+    const double lhs = L + r.a64[(size_t)pp * N + p];  // the fold's own add, viterbi.rs:15
+    const double rhs = (rt + cap) + C;
+    ok = ok && (lhs - rhs > sigma(t, absfin(rt) + __builtin_fabs(cap) + __builtin_fabs(C) + __builtin_fabs(lhs)));
+    L = lhs + r.et64[(size_t)o * N + p];  // (d + a) + b, viterbi.rs:15-17
+    const double ct = r.cb[o], mt = (double)mu[t];
+    const double s = __builtin_fabs(C) + __builtin_fabs(ct) + __builtin_fabs(mt);
+    C = ((C + ct) + mt) + 0x1p-50 * s;
+    pp = p;
+  }
+  const double E = (double)r.e_last[seq];
+  ok = ok && (L - (E + C) > sigma(T, absfin(E) + __builtin_fabs(C) + __builtin_fabs(L)));
+  if (ok) {
+    r.score[seq] = L;
+    r.status[seq] = CVK_SEQ_OK;
+  } else {
+    r.cert[seq] = 2;
+  }
+}
+
+hipError_t launch_ru_fwd2(int np, const RuFwdArgs& fa, int64_t npairs, hipStream_t stream) {
+  if (npairs <= 0) return hipSuccess;
+  if (np != 256) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((trellis_fwd2_f32ru<256>), dim3((unsigned)npairs), dim3(1024), 0, stream, fa);
+  return hipGetLastError();
+}
+
+// lds_reserve as launch_fix_bt
+hipError_t launch_ru_bt(int np, const RuBtArgs& ba, hipStream_t stream, int lds_reserve) {
+  const int64_t n = ba.seq_end - ba.seq_begin;
+  if (n <= 0) return hipSuccess;
+  if (np != 256) return hipErrorInvalidValue;
+  if (lds_reserve > 0)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&backtrack_f32ru<256>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  hipLaunchKernelGGL((backtrack_f32ru<256>), dim3((unsigned)((n + 3) / 4)), dim3(256), (size_t)lds_reserve, stream, ba);
+  return hipGetLastError();
+}
+
+hipError_t launch_ru_score(const RuScoreArgs& r, hipStream_t stream, int lds_reserve) {
+  const int64_t n = r.seq_end - r.seq_begin;
+  if (n <= 0) return hipSuccess;
+  if (lds_reserve > 0)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ru_score_f64), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              160 * 1024);
+  hipLaunchKernelGGL(ru_score_f64, dim3((unsigned)((n + 63) / 64)), dim3(64), (size_t)lds_reserve, stream, r);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------
 // trellis_wave_f32<NPW, FRC>: small N (NPW = 16, 32, 48 or 64 padded states) -- ONE WAVE per
 // sequence, forward pass and backtrack fused, no workgroup barrier and no cross-wave anything.
 // Forward: lane = 4cq + rg holds rows [R·rg, R·rg + R) (R = NPW/4) of the C = NPW/16 columns

@@ -63,6 +63,8 @@ struct Tuning {
   int t64_lo_every = 8;        // low planes of the delta rows at every K-th row and the last (1: every row; <= 16)
   int t64_fixed_first = 16777216;  // certified fixed-point first pass of the plain f64 batch decode: the fewest
                                // elements (sum of lengths) of a call that takes it (0: never)
+  int t64_f32ru_first = 16777216;  // certified f32 round-up first pass: the fewest elements of a call that takes it
+                               // instead of the integer pass (0: never; a call below it follows t64_fixed_first)
   int t64_fixed_chunks = 8;    // the pass's chunks pipelined over two streams, at least min(this, nseq / 2048)
                                // (<= 64); 0: back to back on one stream, one chunk under the workspace cap
   // ---- generic and wide kernels (kernels/trellis.hip) ----

@@ -294,6 +294,33 @@ def last_fixed_first_stats(hmm: HMM) -> dict:
     return {k: int(out[i]) for i, k in enumerate(FIXED_FIRST_STATS[:n])}
 
 
+FIRST_PASS_KINDS = ("none", "fixed", "f32ru")
+
+
+def last_first_pass_kind(hmm: HMM) -> str:
+    """Which certified first pass the last decode_batch[_device] call on this handle took
+    (cv_last_first_pass_kind): "none", "fixed" (t64_fixed_first) or "f32ru" (t64_f32ru_first)."""
+    k = L.lib().cv_last_first_pass_kind(hmm.handle)
+    if k < 0:
+        L.check(L.CV_EINVAL)
+    return FIRST_PASS_KINDS[k]
+
+
+def f32ru_trace(hmm: HMM, obs) -> dict:
+    """Test hook (cv_f32ru_trace): the f32 round-up pass's forward and certificate backtrack on
+    obs [S, T] (the last of an odd S is left out, its outputs 0), and everything they store: rows [T, S, N], mu and r [S, T], E [S],
+    path [S, T]."""
+    obs = np.ascontiguousarray(obs, np.int32)
+    S, T = obs.shape
+    N = hmm.nstates()
+    rows = np.empty((S, T, N), np.float32)
+    mu, r = np.empty((S, T), np.float32), np.empty((S, T), np.float32)
+    E, path = np.empty(S, np.float32), np.empty((S, T), np.int32)
+    ptr = lambda x: x.ctypes.data_as(ctypes.c_void_p)
+    L.check(L.lib().cv_f32ru_trace(hmm.handle, S, T, ptr(obs), ptr(rows), ptr(mu), ptr(r), ptr(E), ptr(path)))
+    return dict(rows=rows.transpose(1, 0, 2), mu=mu, r=r, E=E, path=path)
+
+
 def device_memory() -> dict:
     """Device bytes this process's library holds now and at most (cv_device_memory)."""
     cur, peak = ctypes.c_int64(), ctypes.c_int64()

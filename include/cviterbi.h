@@ -223,7 +223,12 @@ CV_API void cv_hmm_destroy(cv_hmm* h);
  *                         f64 kernels (cv_last_fixed_first_stats).  Such a call waits for its stream
  *                         once.  A handle that left more than 1 in 8 sequences of a call uncertified
  *                         stays on the f64 kernels from then on.  0: never (the earlier behaviour)
- *   t64_fixed_chunks 8    that pass in chunks pipelined over two streams: at least
+ *   t64_f32ru_first 16777216   the same calls: one of at least this many elements takes the
+ *                         certified f32 round-up first pass instead (every f32 add rounded toward +inf,
+ *                         so every row is an upper bound; the f64 fold along the path certifies it);
+ *                         a call below it follows t64_fixed_first.  Same counters, guard and fallback
+ *                         (cv_last_first_pass_kind says which pass ran).  0: never
+ *   t64_fixed_chunks 8    either pass in chunks pipelined over two streams: at least
  *                         min(this, sequences / 2048) chunks (<= 64) out of a double-buffered workspace
  *                         (each chunk half the workspace cap), a chunk's certificate backtrack and score
  *                         beside the next chunk's forward.  0: the chunks back to back on the caller's
@@ -316,6 +321,18 @@ CV_API int32_t cv_last_t64_stats(const cv_hmm* h, int64_t* out, int32_t n);
  * certified; 2 sequences decoded by the f64 kernels (1 + 2 = the call's sequences when word 0
  * is 1); 3 whether the handle's guard has pinned it to the f64 kernels. */
 CV_API int32_t cv_last_fixed_first_stats(const cv_hmm* h, int64_t* out, int32_t n);
+/* Which certified first pass the last cv_decode_batch[_device] call on this handle ran (word 0 of
+ * cv_last_fixed_first_stats is 1 exactly where this is not 0): 0 none, 1 the 32-bit
+ * fixed-point pass (t64_fixed_first), 2 the f32 round-up pass (t64_f32ru_first); -1 on a null
+ * handle. */
+CV_API int32_t cv_last_first_pass_kind(const cv_hmm* h);
+/* Test hook of the f32 round-up pass: its forward and certificate backtrack on nseq >= 2
+ * sequences of one length T (nseq * T <= 2^22; the last of an odd count is left out as in a
+ * decode, its outputs 0), observations in range, and everything they store
+ * copied to the host: rows [nseq * T][N], the shifts mu and the losing candidates r [nseq * T]
+ * (element 0 of a sequence is 0), e_last [nseq], path [nseq * T]. */
+CV_API cv_status cv_f32ru_trace(cv_hmm* h, int64_t nseq, int64_t T, const int32_t* obs, float* rows, float* mu,
+                                float* r, float* e_last, int32_t* path);
 /* Device timings of the last decode call on this handle (synchronizes its events). */
 CV_API cv_status cv_last_timing(cv_hmm* h, cv_timing* out);
 /* Device timings summed over EVERY decode call on this handle from cv_timing_begin to

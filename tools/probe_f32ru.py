@@ -1,0 +1,256 @@
+"""Probe (CPU, numpy): certified f32 round-up first pass for the exact f64 decode.
+
+The numpy model of DESIGN.md "Certified f32 round-up first pass", which the kernels
+(trellis_fwd2_f32ru, backtrack_f32ru, ru_score_f64) follow bit for bit, and the gate-1
+measurement: on config 4's first B sequences, the share that certifies -- beside the integer
+model's (tools/probe_fixed_first.py) on the same sequences -- and that every certified path is
+the f64 decode's own path.
+
+RU(x) is x rounded toward +inf to f32 (-inf stays -inf).  Every stored value is an UPPER bound of
+the real-number recurrence, whatever the shifts, and the certificate compares the exact f64 fold
+along the candidate path (a lower bound of the f64 recurrence's own entry) with those bounds.
+
+Tables (host, f64; G = 2^-16):
+  ca_j = rint(max_i a[i,j] / G) G,   a'[i,j]  = RU(a[i,j] - ca_j)
+  cb_o = rint(max_j fl(b[j,o] + ca_j) / G) G,   b''[j,o] = RU(b[j,o] + (ca_j - cb_o))
+  pi'[j] = RU(pi[j] - ca_j)            (a column or observation of -inf alone: shift 0)
+  (ca_j - cb_o is exact on the grid, so each entry is ONE real sum, rounded up exactly.)
+Rows:
+  v_0[j] = RU(pi'[j] + b''[j,o_0])
+  mu_t = max(max_j v_{t-1}[j], -FLT_MAX);  m = max_i RU(v_{t-1}[i] + a'[i,j]);
+  x = RU(m + b''[j,o_t]);  v_t[j] = RU(x - mu_t)
+  C_0 = cb_{o_0};  C_t = C_{t-1} + cb_{o_t} + mu_t;   v_t[j] + C_t >= D_t[j] (the real recurrence)
+Backtrack (RU adds):
+  j* = first argmax of v_{T-1}, E = the largest other entry;
+  step t into cur = p_t: s_i = RU(v_{t-1}[i] + a'[i,cur]), w = first argmax, p_{t-1} = w,
+  r_t = the largest s_i with i != w
+Certificate (f64, beside the fold L_0 = pi[p_0] + b[p_0,o_0], L_t = (L_{t-1} + a) + b):
+  step t:  lhs = fl(L_{t-1} + a[p_{t-1},p_t]),  rhs = (r_t + ca_{p_t}) + Chat_{t-1},
+           lhs - rhs > sigma(t, |r_t| + |ca| + |Chat| + |lhs|)
+  end:     L_{T-1} - (E + Chat_{T-1}) > sigma(T, |E| + |Chat| + |L|)
+  sigma(n, s) = 4 u W (n + 2)^2 + 2^-49 s,  u = 2^-53, W = max|pi| + max|a| + max|b| (finite)
+  Chat_t = (Chat_{t-1} + cb_{o_t}) + mu_t, then + 2^-50 (|Chat_{t-1}| + |cb_{o_t}| + |mu_t|)
+  (an infinite r_t or E counts 0 in s: the comparison is then +inf > sigma, or NaN and fails).
+
+Usage: python tools/probe_f32ru.py [B] [chunk]
+"""
+import importlib.util
+import os
+import sys
+import time
+
+import numpy as np
+
+GRID = 65536.0  # the shifts are multiples of 2^-16
+GRID_MAX = 2.0 ** 30  # |shift| below this: sums and differences of two shifts are exact in f64
+FLT_MAX = np.float32(3.4028234663852886e38)
+U = 2.0 ** -53
+F32 = np.float32
+
+
+def two_sum_err(x, y, s):
+    """The exact error of s = fl(x + y) in f64 (0 where s is not finite)."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        bb = s - x
+        e = (x - (s - bb)) + (y - bb)
+    return np.where(np.isfinite(s), e, 0.0)
+
+
+def ru32(s, err=None):
+    """The smallest f32 >= s + err (s f64, err the sign-carrying remainder of an exact sum)."""
+    s = np.asarray(s, np.float64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        f = s.astype(F32)
+    back = f.astype(np.float64)
+    low = back < s
+    if err is not None:
+        low |= (back == s) & (err > 0)
+    return np.where(low, np.nextafter(f, F32(np.inf)), f).astype(F32)
+
+
+def ru_add(x, y):
+    """RU(x + y) for f32 arrays, exact for every pair of operands (two-sum where f64 rounds)."""
+    x = np.asarray(x, F32).astype(np.float64)
+    y = np.asarray(y, F32).astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        s = x + y
+    return ru32(s, two_sum_err(x, y, s))
+
+
+def rn_add(x, y):
+    """Round-to-nearest f32 add (the control the GPU test uses to show the mode is in force)."""
+    return (np.asarray(x, F32) + np.asarray(y, F32)).astype(F32)
+
+
+def ru_sum64(x, y):
+    """RU to f32 of the real sum of two f64 arrays."""
+    x, y = np.broadcast_arrays(np.asarray(x, np.float64), np.asarray(y, np.float64))
+    with np.errstate(invalid="ignore"):
+        s = x + y
+    return ru32(s, two_sum_err(x, y, s))
+
+
+def _grid(x):
+    """rint(x / G) G; a maximum of -inf alone -> 0."""
+    x = np.asarray(x, np.float64)
+    return np.where(np.isfinite(x), np.rint(np.where(np.isfinite(x), x, 0.0) * GRID) / GRID, 0.0)
+
+
+def tables(pi, a, b):
+    """dict: ca [N], cb [V], a1 [N,N] f32, b2 [N,V] f32, p1 [N] f32, ks = 4 u W; None if a shift is
+    outside the grid's exact range."""
+    pi, a, b = (np.asarray(m, np.float64) for m in (pi, a, b))
+    ca = _grid(a.max(axis=0))
+    cb = _grid((b + ca[:, None]).max(axis=0))
+    if max(np.abs(ca).max(), np.abs(cb).max()) >= GRID_MAX:
+        return None
+    w = 0.0
+    for m in (pi, a, b):
+        f = np.isfinite(m)
+        w += float(np.abs(m[f]).max()) if f.any() else 0.0
+    return dict(ca=ca, cb=cb, a1=ru_sum64(a, -ca[None, :]), b2=ru_sum64(b, ca[:, None] - cb[None, :]),
+                p1=ru_sum64(pi, -ca), ks=4.0 * U * w)
+
+
+def _exact_in_f64(*arrs):
+    """True if every sum of two finite entries of the f32 arrays is exact in f64."""
+    lo, hi = np.inf, 0.0
+    for x in arrs:
+        m = np.abs(x[np.isfinite(x) & (x != 0)])
+        if m.size:
+            lo, hi = min(lo, float(m.min())), max(hi, float(m.max()))
+    return hi == 0.0 or hi / lo < 2.0 ** 27
+
+
+def forward(tb, obs, add=ru_add):
+    """obs [S, T]; rows [T, S, N] f32 and mu [S, T] f32 (mu[:, 0] = 0, unused)."""
+    a1, b2, p1 = tb["a1"], tb["b2"], tb["p1"]
+    S, T = obs.shape
+    N = a1.shape[0]
+    rows = np.empty((T, S, N), F32)
+    mu = np.zeros((S, T), F32)
+    v = add(p1[None, :], b2[:, obs[:, 0]].T)
+    rows[0] = v
+    a64 = a1.astype(np.float64)
+    for t in range(1, T):
+        m_t = np.maximum(v.max(axis=1), -FLT_MAX)
+        if add is ru_add and _exact_in_f64(v, a1):
+            # RU is monotone and the f64 sums are exact: the maximum of the sums, rounded once
+            with np.errstate(invalid="ignore"):
+                m = ru32((v.astype(np.float64)[:, :, None] + a64[None, :, :]).max(axis=1))
+        else:
+            m = add(v[:, :, None], a1[None, :, :]).max(axis=1)
+        x = add(m, b2[:, obs[:, t]].T)
+        v = add(x, -m_t[:, None])
+        rows[t], mu[:, t] = v, m_t
+    return rows, mu
+
+
+def _top2(x):
+    """first argmax, and the largest value among the other indices; x [S, N] f32."""
+    S = x.shape[0]
+    w = x.argmax(axis=1)
+    y = x.copy()
+    y[np.arange(S), w] = -np.inf
+    return w, y.max(axis=1)
+
+
+def backtrack(tb, rows, add=ru_add):
+    """path [S, T], r [S, T] f32 (r[:, 0] = 0, unused), E [S] f32."""
+    T, S, N = rows.shape
+    path = np.empty((S, T), np.int64)
+    r = np.zeros((S, T), F32)
+    cur, E = _top2(rows[T - 1])
+    path[:, T - 1] = cur
+    for t in range(T - 1, 0, -1):
+        w, r[:, t] = _top2(add(rows[t - 1], tb["a1"][:, cur].T))
+        path[:, t - 1] = cur = w
+    return path, r, E
+
+
+def _absfin(x):
+    x = np.asarray(x, np.float64)
+    return np.where(np.isinf(x), 0.0, np.abs(x))
+
+
+def certify(pi, a, b, tb, obs, mu, path, r, E):
+    """cert [S] bool, score [S] f64: the fold along the path and the certificate beside it."""
+    S, T = obs.shape
+    ca, cb, ks = tb["ca"], tb["cb"], tb["ks"]
+    mu, r, E = (np.asarray(x, np.float64) for x in (mu, r, E))
+
+    def sigma(n, s):
+        return ks * ((n + 2.0) * (n + 2.0)) + 2.0 ** -49 * s
+
+    with np.errstate(invalid="ignore"):
+        p = path[:, 0]
+        L = pi[p] + b[p, obs[:, 0]]
+        C = cb[obs[:, 0]].copy()
+        ok = np.ones(S, bool)
+        for t in range(1, T):
+            pp, p = p, path[:, t]
+            lhs = L + a[pp, p]
+            rhs = (r[:, t] + ca[p]) + C
+            ok &= (lhs - rhs) > sigma(t, _absfin(r[:, t]) + np.abs(ca[p]) + np.abs(C) + np.abs(lhs))
+            L = lhs + b[p, obs[:, t]]
+            c_t = cb[obs[:, t]]
+            s = np.abs(C) + np.abs(c_t) + np.abs(mu[:, t])
+            C = ((C + c_t) + mu[:, t]) + 2.0 ** -50 * s
+        ok &= (L - (E + C)) > sigma(T, _absfin(E) + np.abs(C) + np.abs(L))
+    return ok, L
+
+
+def decode(pi, a, b, obs):
+    """The whole first pass for sequences of one length: path [S, T], cert [S], score [S], parts."""
+    tb = tables(pi, a, b)
+    rows, mu = forward(tb, obs)
+    path, r, E = backtrack(tb, rows)
+    cert, score = certify(np.asarray(pi, np.float64), np.asarray(a, np.float64), np.asarray(b, np.float64), tb, obs,
+                          mu, path, r, E)
+    return path, cert, score, dict(rows=rows, mu=mu, r=r, E=E, tb=tb)
+
+
+def _load_fixed_model():
+    spec = importlib.util.spec_from_file_location(
+        "probe_fixed_first", os.path.join(os.path.dirname(os.path.abspath(__file__)), "probe_fixed_first.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
+
+
+def main():
+    sys.path.insert(0, "consistent-viterbi_amd")
+    from cviterbi import synth
+
+    FX = _load_fixed_model()
+    B = int(sys.argv[1]) if len(sys.argv) > 1 else 512
+    chunk = int(sys.argv[2]) if len(sys.argv) > 2 else 32
+    c = synth.config("c4", B)
+    pi, a, b = c["pi"], c["a"], c["b"]
+    T = 512
+    obs = c["obs"].reshape(B, T).astype(np.int64)
+    certs, certs_i, same, gaps, excess = [], [], [], [], []
+    t0 = time.time()
+    for s0 in range(0, B, chunk):
+        o = obs[s0:s0 + chunk]
+        p64, g64 = FX.decode64(pi, a, b, o)
+        pr, cert, _, _ = decode(pi, a, b, o)
+        _, cert_i, _ = FX.decode(pi, a, b, o)
+        eq = (pr == p64).all(axis=1)
+        assert np.all(eq[cert]), "a certified round-up path differs from the f64 path"
+        certs.append(cert); certs_i.append(cert_i); same.append(eq); gaps.append(g64)
+        print(f"{s0 + len(o)}/{B} seqs, {time.time() - t0:.0f} s: certified {np.concatenate(certs).mean():.4f}"
+              f" (integer model {np.concatenate(certs_i).mean():.4f}), path == f64 {np.concatenate(same).mean():.4f}",
+              flush=True)
+    cert = np.concatenate(certs); cert_i = np.concatenate(certs_i); eq = np.concatenate(same); g = np.concatenate(gaps)
+    print(f"\nB={B} N=256 T=512 (config 4, first {B} sequences), f32 round-up first pass")
+    print(f"f64 path margin quantiles 1/5/10/50% = {np.quantile(g, [0.01, 0.05, 0.10, 0.5])}")
+    print(f"round-up path == f64 path {eq.mean():.4f}; CERTIFIED {cert.mean():.4f} ({cert.sum()} of {B});"
+          f" integer model {cert_i.mean():.4f} ({cert_i.sum()} of {B})")
+    print(f"certified paths equal to the f64 path: {int((eq & cert).sum())} of {int(cert.sum())}")
+    print(f"projected fallback of 65,536: {(1 - cert.mean()) * 65536:.0f} sequences")
+    print(f"uncertified margins (f64): {np.sort(g[~cert])}")
+
+
+if __name__ == "__main__":
+    main()
