@@ -295,6 +295,9 @@ struct cv_hmm {
   // host API's gamma staging
   DevBuf ps_rows, ps_order, st_gamma;
   DevBuf ps_kshift;  // cv_posterior_emissions*: each sequence's sum of row-scale exponents (int64)
+  // cv_expected_counts*: the GEMM's partial tiles, the call's NP x NP accumulator, gamma_0 of every
+  // sequence, and the host API's staging of pi_cnt [N] and a_cnt [N][N]
+  DevBuf ps_xi_part, ps_xi_s, ps_g0, st_cnt;
   PinnedHost sm_pin;  // cv_sample_batch: the log-likelihoods and score planes on their way to the caller
   OrderStage ps_pin;
   // K-best workspace: the u16 back-pointers of one chunk, each sequence's last lists, the
@@ -1475,6 +1478,11 @@ struct SampleReq {
   int32_t* path;  // device, [draws][offsets[nseq]]
   double* score;  // device, [draws][nseq], nullable
 };
+// cv_expected_counts*: the counts arm of the backward pass and the kernels behind it
+struct CountsReq {
+  double* pi_cnt;  // device, [N]
+  double* a_cnt;   // device, [N][N]
+};
 
 // Core of cv_posterior_batch*: all pointers are device pointers except offsets_host.  Chunks of
 // whole sequences (original order) whose forward rows fit the workspace cap run forward then
@@ -1487,10 +1495,14 @@ struct SampleReq {
 // smp (cv_sample_batch*): the rows are stored and each chunk's backward pass is replaced by the
 // sampler's walk and the scores of its paths; everything else -- planning, order, events -- is
 // this function's, so a sampling call chunks and times exactly like a posterior call.
+// cnt (cv_expected_counts*): the backward pass runs with its counts arm (8 NP + 8 bytes per
+// element more: the U row and 1 / rsum), each chunk's rows then go through the count GEMM and its
+// fold into ps_xi_s (zeroed here), and the last chunk is followed by the kernels that write
+// pi_cnt and a_cnt -- all inside the chunk's backward events, so bt_ms covers them.
 cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, const int64_t* offsets_dev,
                            const int32_t* obs_dev, const cv_opts& o, double* loglik_dev, int32_t* path_dev,
                            double* gamma_dev, uint8_t* status_dev, hipStream_t stream, const EmisSrc* emis = nullptr,
-                           const SampleReq* smp = nullptr) {
+                           const SampleReq* smp = nullptr, const CountsReq* cnt = nullptr) {
   cv_status st = posterior_opts_ok(h, o);
   if (st != CV_OK) return st;
   if (smp && smp->score && (st = ensure_f64_tables(h)) != CV_OK) return st;
@@ -1503,19 +1515,32 @@ cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
   h->last_kernel = generic ? CV_KERNEL_GENERIC : CV_KERNEL_AUTO;
   h->last_np = np;
   h->last_mt = generic ? -1 : cvp::kPostGroup;
+  if (nseq == 0 && cnt) {  // overwritten, not accumulated: an empty batch counts nothing
+    HIP_TRY(hipMemsetAsync(cnt->pi_cnt, 0, (size_t)h->N * 8, stream));
+    HIP_TRY(hipMemsetAsync(cnt->a_cnt, 0, (size_t)h->N * h->N * 8, stream));
+  }
   if (nseq == 0) return CV_OK;
   if (h->ws_rec) HIP_TRY(hipStreamWaitEvent(stream, h->ws_done, 0));
 
-  const bool store = path_dev || gamma_dev || smp;
+  const bool store = path_dev || gamma_dev || smp || cnt;
   const uint64_t row_bytes = (uint64_t)np * 8;
-  const uint64_t per_elem = (store ? row_bytes : 0) + (emis ? row_bytes + 4 : 0);
+  // counts: the U row and inv of every element beside its forward row
+  const uint64_t per_elem = (store ? row_bytes : 0) + (cnt ? row_bytes + 8 : 0) + (emis ? row_bytes + 4 : 0);
+  // ... and the GEMM's partial tiles, under the same cap: at most cvp::kXiPartCap, and half of a
+  // cap that is smaller than twice that
+  uint64_t part_cap = 0;
   std::vector<cvplan::Chunk> chunks;
   uint64_t max_elems = 0;
   if (per_elem == 0) {
     chunks.emplace_back(0, nseq);
   } else {
     // 2 KiB of rows per element at N = 256: the f64 trellis's default cap (HBM3E: 288 GB per GPU)
-    const uint64_t cap = o.workspace_bytes ? o.workspace_bytes : default_workspace_cap(h->ps_rows.bytes, kDefaultWorkspaceT64);
+    uint64_t cap = o.workspace_bytes ? o.workspace_bytes : default_workspace_cap(h->ps_rows.bytes, kDefaultWorkspaceT64);
+    if (cnt) {
+      const uint64_t most = std::min<uint64_t>(cvp::kXiPartCap, (uint64_t)cvp::kXiMaxParts * np * row_bytes);
+      part_cap = cap >= 2 * most ? most : cap / 2;
+      cap -= part_cap;
+    }
     uint64_t elem_cap = cap / per_elem;
     if (emis) {  // the staged rows of a sequence cannot be split, and a chunk is indexed by int32
       elem_cap = std::min<uint64_t>(elem_cap, INT32_MAX);
@@ -1530,11 +1555,33 @@ cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
     max_elems = std::max<uint64_t>(cvplan::split_equal_shares(offsets_host, nseq, elem_cap, chunks).max_elems, 1);
     if ((st = h->ps_rows.ensure((size_t)(max_elems * per_elem))) != CV_OK) return st;
   }
-  // the workspace: [max_elems][NP] forward rows (store), [max_elems][NP] staged emission rows,
-  // [max_elems] int32 observation indices (emis); NP * 8 is a multiple of 512
-  double* const ws_rows = store ? h->ps_rows.as<double>() : nullptr;
-  double* const ws_emis = emis ? h->ps_rows.as<double>() + (store ? max_elems * (uint64_t)np : 0) : nullptr;
-  int32_t* const ws_idx = emis ? reinterpret_cast<int32_t*>(ws_emis + max_elems * (uint64_t)np) : nullptr;
+  // the workspace: [max_elems][NP] forward rows (store), [max_elems][NP] U rows (counts),
+  // [max_elems][NP] staged emission rows (emis), [max_elems] inv (counts), [max_elems] int32
+  // observation indices (emis); NP * 8 is a multiple of 512
+  double* ws_next = h->ps_rows.as<double>();
+  auto take_rows = [&](bool on, uint64_t width) {
+    double* const p = on ? ws_next : nullptr;
+    if (on) ws_next += max_elems * width;
+    return p;
+  };
+  double* const ws_rows = take_rows(store, (uint64_t)np);
+  double* const ws_urows = take_rows(cnt != nullptr, (uint64_t)np);
+  double* const ws_emis = take_rows(emis != nullptr, (uint64_t)np);
+  double* const ws_inv = take_rows(cnt != nullptr, 1);
+  int32_t* const ws_idx = emis ? reinterpret_cast<int32_t*>(ws_next) : nullptr;
+  const int64_t xi_key = cvk::tuning().xi_part_rows;
+  if (cnt) {
+    int64_t most_parts = 1;
+    for (const auto& c : chunks) {
+      const int64_t rows = offsets_host[c.second] - offsets_host[c.first];
+      const int64_t per = cvp::post_xi_part_rows(rows, np, xi_key, part_cap);
+      most_parts = std::max(most_parts, (rows + per - 1) / per);
+    }
+    if ((st = h->ps_xi_part.ensure((size_t)most_parts * np * row_bytes)) != CV_OK) return st;
+    if ((st = h->ps_xi_s.ensure((size_t)np * row_bytes)) != CV_OK) return st;
+    if ((st = h->ps_g0.ensure((size_t)nseq * row_bytes)) != CV_OK) return st;
+    HIP_TRY(hipMemsetAsync(h->ps_xi_s.p, 0, (size_t)np * row_bytes, stream));
+  }
   if (emis) {
     if ((st = h->ps_kshift.ensure((size_t)nseq * 8)) != CV_OK) return st;
     HIP_TRY(hipMemsetAsync(h->ps_kshift.p, 0, (size_t)nseq * 8, stream));
@@ -1573,6 +1620,11 @@ cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
     g.path = path_dev;
     g.gamma = gamma_dev;
     g.dump = h->p_dump.as<double>();
+    if (cnt) {
+      g.urows = ws_urows;
+      g.inv = ws_inv;
+      g.g0 = h->ps_g0.as<double>();
+    }
     hipEvent_t f0 = h->ev[eb + 4 * ci], f1 = h->ev[eb + 4 * ci + 1], b0 = h->ev[eb + 4 * ci + 2], b1 = h->ev[eb + 4 * ci + 3];
     HIP_TRY(hipEventRecord(f0, stream));
     hipError_t err;
@@ -1644,6 +1696,33 @@ cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
     } else if (store) {
       err = cvp::launch_post_bwd(g, generic, stream);
       if (err != hipSuccess) return set_err(CV_EDEVICE, "posterior backward launch failed: %s", hipGetErrorString(err));
+    }
+    if (cnt) {
+      cvp::XiArgs x{};
+      x.rows = ws_rows;
+      x.urows = ws_urows;
+      x.inv = ws_inv;
+      x.nrows = offsets_host[c.second] - offsets_host[c.first];
+      x.part_rows = cvp::post_xi_part_rows(x.nrows, np, xi_key, part_cap);
+      x.nparts = (x.nrows + x.part_rows - 1) / x.part_rows;
+      x.np = np;
+      x.part = h->ps_xi_part.as<double>();
+      x.s = h->ps_xi_s.as<double>();
+      err = cvp::launch_post_xi(x, stream);
+      if (err == hipSuccess && ci + 1 == chunks.size()) {
+        cvp::CountsFinalArgs f{};
+        f.s = x.s;
+        f.a = g.a;
+        f.g0 = g.g0;
+        f.status = status_dev;
+        f.nseq = nseq;
+        f.nstates = h->N;
+        f.np = np;
+        f.a_cnt = cnt->a_cnt;
+        f.pi_cnt = cnt->pi_cnt;
+        err = cvp::launch_post_counts_final(f, stream);
+      }
+      if (err != hipSuccess) return set_err(CV_EDEVICE, "expected-counts launch failed: %s", hipGetErrorString(err));
     }
     HIP_TRY(hipEventRecord(b1, stream));
     h->last_launches = (int64_t)ci + 1;
@@ -1957,7 +2036,7 @@ CV_API cv_status cv_hmm_release_workspaces(cv_hmm* h) {
                     &h->chainb.rpsi, &h->chainb.rows, &h->chainb.small, &h->chainb.rpath, &h->chainb.soff,
                     &h->chainb.sobs, &h->chainb.spath, &h->chainb.sres, &h->chainb.sinit, &h->chainb.slast,
                     &h->chainb.spsi, &h->ps_rows,
-                    &h->ps_order, &h->ps_kshift, &h->st_gamma, &h->kb_bp, &h->kb_last, &h->kb_order, &h->kb_end, &h->st_count,
+                    &h->ps_order, &h->ps_kshift, &h->st_gamma, &h->ps_xi_part, &h->ps_xi_s, &h->ps_g0, &h->st_cnt, &h->kb_bp, &h->kb_last, &h->kb_order, &h->kb_end, &h->st_count,
                     &h->st_emis, &h->fx_cert, &h->fx_idx, &h->fx_obs2, &h->fx_path2, &h->fx_score2, &h->fx_status2,
                     &h->ru_mu, &h->ru_r, &h->ru_e})
     b->release();
@@ -2806,6 +2885,101 @@ CV_API cv_status cv_posterior_emissions(cv_hmm* h, int64_t nseq, const int64_t* 
     if (status_out[s] == CV_SEQ_INFEASIBLE)
       return set_err(CV_EINFEASIBLE, "sequence %lld has likelihood 0", (long long)s);
   return CV_OK;
+}
+
+// ---- expected counts for EM: cv_expected_counts* -----------------------------------------------
+// The posterior entries with the counts request in place of the path: the same checks, staging
+// and INFEASIBLE report; pi_cnt [N] and a_cnt [N][N] come back through st_cnt.
+static cv_status counts_device_entry(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, const int64_t* offsets_dev,
+                                     const int32_t* obs_dev, const double* emis_dev, int64_t ld, bool dense,
+                                     const cv_opts* opts, double* loglik_dev, double* pi_cnt_dev, double* a_cnt_dev,
+                                     double* gamma_dev, uint8_t* status_dev) {
+  if (!h) return set_err(CV_EINVAL, "null handle");
+  if (nseq < 0) return set_err(CV_EINVAL, "nseq < 0");
+  if (!pi_cnt_dev || !a_cnt_dev) return set_err(CV_EINVAL, "null device buffer");
+  if (nseq > 0 && (!offsets_dev || !(dense ? (const void*)emis_dev : (const void*)obs_dev) || !loglik_dev || !status_dev))
+    return set_err(CV_EINVAL, "null device buffer");
+  const cv_opts o = opts ? *opts : default_opts();
+  cv_status st = dense ? posterior_emissions_args_ok(h, ld, o) : posterior_opts_ok(h, o);
+  if (st != CV_OK) return st;
+  CV_LOCK(h);
+  if ((st = set_device(h)) != CV_OK) return st;
+  hipStream_t stream = o.stream ? (hipStream_t)o.stream : h->stream;
+  const EmisSrc src{emis_dev, ld};
+  const CountsReq cnt{pi_cnt_dev, a_cnt_dev};
+  return posterior_device(h, nseq, offsets_host, offsets_dev, dense ? nullptr : obs_dev, o, loglik_dev, nullptr, gamma_dev,
+                          status_dev, stream, dense ? &src : nullptr, nullptr, &cnt);
+}
+
+static cv_status counts_host_entry(cv_hmm* h, int64_t nseq, const int64_t* offsets, const int32_t* obs,
+                                   const double* emis, int64_t ld, bool dense, const cv_opts* opts, double* loglik_out,
+                                   double* pi_cnt_out, double* a_cnt_out, double* gamma_out, uint8_t* status_out) {
+  if (!h) return set_err(CV_EINVAL, "null handle");
+  if (nseq < 0 || !pi_cnt_out || !a_cnt_out) return set_err(CV_EINVAL, "null argument");
+  if (nseq > 0 && (!offsets || !(dense ? (const void*)emis : (const void*)obs) || !loglik_out || !status_out))
+    return set_err(CV_EINVAL, "null argument");
+  cv_opts o = opts ? *opts : default_opts();
+  cv_status st = dense ? posterior_emissions_args_ok(h, ld, o) : posterior_opts_ok(h, o);
+  if (st != CV_OK) return st;
+  CV_LOCK(h);
+  if ((st = set_device(h)) != CV_OK) return st;
+  const size_t N = (size_t)h->N;
+  if (nseq == 0) {  // overwritten, not accumulated
+    std::fill(pi_cnt_out, pi_cnt_out + N, 0.0);
+    std::fill(a_cnt_out, a_cnt_out + N * N, 0.0);
+    return CV_OK;
+  }
+  HostBatch hb{h, nseq, offsets, dense ? nullptr : obs, o.stream ? (hipStream_t)o.stream : h->stream};
+  if ((st = hb.stage(o, 0, 1)) != CV_OK) return st;
+  if (gamma_out && (st = h->st_gamma.ensure(hb.plane() * N * 8)) != CV_OK) return st;
+  if ((st = h->st_cnt.ensure((N + N * N) * 8)) != CV_OK) return st;
+  EmisSrc src{};
+  if (dense && (st = hb.stage_emis(emis, ld, &src)) != CV_OK) return st;
+  const CountsReq cnt{h->st_cnt.as<double>(), h->st_cnt.as<double>() + N};
+  st = posterior_device(h, nseq, offsets, h->st_off.as<int64_t>(), dense ? nullptr : h->st_obs.as<int32_t>(), o,
+                        h->st_score.as<double>(), nullptr, gamma_out ? h->st_gamma.as<double>() : nullptr,
+                        h->st_status.as<uint8_t>(), hb.stream, dense ? &src : nullptr, nullptr, &cnt);
+  if (st != CV_OK) return hb.fail(st);
+  if (gamma_out) hb.fetch_elems(gamma_out, h->st_gamma, N);
+  hb.fetch_seqs(loglik_out, h->st_score);
+  hb.fetch_seqs(status_out, h->st_status);
+  if (hb.err == hipSuccess) hb.err = hipMemcpyAsync(pi_cnt_out, cnt.pi_cnt, N * 8, hipMemcpyDeviceToHost, hb.stream);
+  if (hb.err == hipSuccess) hb.err = hipMemcpyAsync(a_cnt_out, cnt.a_cnt, N * N * 8, hipMemcpyDeviceToHost, hb.stream);
+  if ((st = hb.finish()) != CV_OK) return st;
+  for (int64_t s = 0; s < nseq; ++s)
+    if (status_out[s] == CV_SEQ_INFEASIBLE)
+      return set_err(CV_EINFEASIBLE, "sequence %lld has likelihood 0", (long long)s);
+  return CV_OK;
+}
+
+CV_API cv_status cv_expected_counts_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
+                                           const int64_t* offsets_dev, const int32_t* obs_dev, const cv_opts* opts,
+                                           double* loglik_dev, double* pi_cnt_dev, double* a_cnt_dev, double* gamma_dev,
+                                           uint8_t* status_dev) {
+  return counts_device_entry(h, nseq, offsets_host, offsets_dev, obs_dev, nullptr, 0, false, opts, loglik_dev, pi_cnt_dev,
+                             a_cnt_dev, gamma_dev, status_dev);
+}
+
+CV_API cv_status cv_expected_counts(cv_hmm* h, int64_t nseq, const int64_t* offsets, const int32_t* obs,
+                                    const cv_opts* opts, double* loglik_out, double* pi_cnt_out, double* a_cnt_out,
+                                    double* gamma_out, uint8_t* status_out) {
+  return counts_host_entry(h, nseq, offsets, obs, nullptr, 0, false, opts, loglik_out, pi_cnt_out, a_cnt_out, gamma_out,
+                           status_out);
+}
+
+CV_API cv_status cv_expected_counts_emissions_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
+                                                     const int64_t* offsets_dev, const double* emis_dev, int64_t ld,
+                                                     const cv_opts* opts, double* loglik_dev, double* pi_cnt_dev,
+                                                     double* a_cnt_dev, double* gamma_dev, uint8_t* status_dev) {
+  return counts_device_entry(h, nseq, offsets_host, offsets_dev, nullptr, emis_dev, ld, true, opts, loglik_dev, pi_cnt_dev,
+                             a_cnt_dev, gamma_dev, status_dev);
+}
+
+CV_API cv_status cv_expected_counts_emissions(cv_hmm* h, int64_t nseq, const int64_t* offsets, const double* emis,
+                                              int64_t ld, const cv_opts* opts, double* loglik_out, double* pi_cnt_out,
+                                              double* a_cnt_out, double* gamma_out, uint8_t* status_out) {
+  return counts_host_entry(h, nseq, offsets, nullptr, emis, ld, true, opts, loglik_out, pi_cnt_out, a_cnt_out, gamma_out,
+                           status_out);
 }
 
 // ---- consistency-constrained decode --------------------------------------------------------

@@ -10,7 +10,9 @@
 // what a decode returns.  The fitting keys (bw_*) are not bit-identical: the E-step sums are
 // f64 atomic adds in arrival order, so another path, chunking or wave count adds the same terms
 // in another order; they hold to the fitting tolerance (1e-9 on the log10 parameters, as
-// against the oracle).  Handle-less entry points (cv_hmm_fit_*) snapshot the environment per call.
+// against the oracle).  xi_part_rows (cv_expected_counts*) is not bit-identical either: it moves the
+// boundaries of the GEMM's parts, so the same non-negative terms are added in another grouping;
+// the counts hold their bound (include/cviterbi.h) under every value.  Handle-less entry points (cv_hmm_fit_*) snapshot the environment per call.
 #pragma once
 
 #include <cstdint>
@@ -87,6 +89,9 @@ struct Tuning {
                                // of the memory rule (a longer sequence is still a chunk of its own)
   int bw_max_waves = 0;        // > 0: the most backward waves of the N <= 64 kernels (0: 8 per CU); each
                                // wave walks ceil(pairs / waves) pairs of sequences
+  // ---- expected counts (kernels/counts.hip) ----
+  int xi_part_rows = 0;        // > 0: rows per part of post_xi_gemm, rounded up to a multiple of 4 (0: by
+                               // rule, cvp::post_xi_part_rows); a test hook: several parts from a small input
 };
 
 // the current call's tuning: the handle's snapshot inside a host API call, else the defaults

@@ -8,6 +8,8 @@ from .hmm import HMM, tuning_keys  # noqa: F401
 from .decode import (constrained_pairs, constrained_partials, constrained_select, decode, decode_batch, decode_batch_device, decode_constrained_device, decode_constrained_exchange,  # noqa: F401
                      decode_constrained, decode_forced_components, decode_superseq_cp, device_memory, f32ru_trace, last_first_pass_kind, last_suffix_traced, last_fixed_first_stats, last_superseq_stats, last_t64_stats, last_timing, timing_begin,
                      timing_end)
+from .counts import (expected_counts, expected_counts_device, expected_counts_emissions,  # noqa: F401
+                     expected_counts_emissions_device, reestimate)
 from .emissions import decode_emissions, decode_emissions_device  # noqa: F401
 from .emissions import posterior_emissions, posterior_emissions_device, score_emissions  # noqa: F401
 from .fit import fit_mle, fit_train, last_fit_stats  # noqa: F401

@@ -46,6 +46,8 @@ EXPORTS = [
     "cv_kbest_batch", "cv_kbest_batch_device",
     "cv_decode_emissions", "cv_decode_emissions_device",
     "cv_posterior_emissions", "cv_posterior_emissions_device",
+    "cv_expected_counts", "cv_expected_counts_device",
+    "cv_expected_counts_emissions", "cv_expected_counts_emissions_device",
     "cv_sample_batch", "cv_sample_batch_device",
     "cv_last_t64_stats", "cv_last_fixed_first_stats", "cv_hmm_fit_last_stats",
     "cv_last_first_pass_kind", "cv_f32ru_trace",
@@ -136,6 +138,10 @@ def lib():
         "cv_decode_emissions_device": ([P, I64, P, P, P, I64, P, P, P, P], S),
         "cv_posterior_emissions": ([P, I64, P, P, I64, P, P, P, P, P], S),
         "cv_posterior_emissions_device": ([P, I64, P, P, P, I64, P, P, P, P, P], S),
+        "cv_expected_counts": ([P, I64, P, P, P, P, P, P, P, P], S),
+        "cv_expected_counts_device": ([P, I64, P, P, P, P, P, P, P, P, P], S),
+        "cv_expected_counts_emissions": ([P, I64, P, P, I64, P, P, P, P, P, P], S),
+        "cv_expected_counts_emissions_device": ([P, I64, P, P, P, I64, P, P, P, P, P, P], S),
         "cv_last_timing": ([P, P], S),
         "cv_timing_begin": ([P], S),
         "cv_timing_end": ([P, P], S),

@@ -249,6 +249,10 @@ CV_API void cv_hmm_destroy(cv_hmm* h);
  *                         chunk of its own (test hook: several chunks on a small corpus)
  *   bw_max_waves 0        Baum-Welch, N <= 64: > 0 the most backward waves (0: 8 per compute unit);
  *                         each walks ceil(pairs / waves) pairs of sequences (test hook)
+ *   xi_part_rows 0        cv_expected_counts*: > 0 the rows per part of the count GEMM, rounded up to a
+ *                         multiple of 4 (0: by rule, from the chunk's rows and NP); a test hook: several
+ *                         parts from a small input.  Not bit-identical: it regroups the sums of
+ *                         non-negative terms; the counts hold their bound under every value
  * The bw_* keys are not bit-identical: the E-step sums are f64 atomic adds in arrival order, so
  * they hold to the fitting tolerance (1e-9 on the log10 parameters) instead.
  * Unknown keys and values outside int32 are CV_EINVAL.  cv_tuning_key(i) lists the keys
@@ -690,6 +694,72 @@ CV_API cv_status cv_posterior_emissions_device(cv_hmm* h, int64_t nseq, const in
                                                const int64_t* offsets_dev, const double* emis_dev, int64_t ld,
                                                const cv_opts* opts, double* loglik_dev, int32_t* path_dev,
                                                double* gamma_dev, uint8_t* status_dev);
+
+/* ---- expected counts for EM (the E-step's sufficient statistics of pi and A) -------------------
+ * The pairwise posterior of cv_posterior_batch's model: the model is read exactly as there
+ * (VITERBI association, p = 10^x, -inf = 0, a forced element admits only its state).  For every
+ * sequence s with status CV_SEQ_OK, with alpha^, beta^ the scaled forward and backward rows,
+ *   u_t+1 = b(o_t+1) o mask_t+1 o beta^_t+1,   rsum_t = sum_i alpha^_t[i] (A u_t+1)[i],
+ *   xi_t(i, j) = P(s_t = i, s_t+1 = j | o, tags) = alpha^_t[i] A[i][j] u_t+1[j] / rsum_t,  0 <= t < T - 1,
+ *   pi_cnt_out[i]        = sum_s gamma_0(s)[i],
+ *   a_cnt_out[i * N + j] = sum_s sum_t xi_t(s)(i, j)      (from-major).
+ * Sequences with status EMPTY, BADOBS or INFEASIBLE contribute nothing and disturb no other
+ * sequence; a sequence with T = 1 contributes to pi_cnt only.  The outputs are overwritten, not
+ * accumulated (nseq = 0 writes zeros): a multi-GPU caller adds the arrays of its shards.
+ * loglik_out, gamma_out (nullable) and status_out are those of cv_posterior_batch, bit for bit.
+ * How: the backward pass also stores u_t+1 and 1 / rsum_t per element; per chunk one f64
+ * matrix-core GEMM forms S = sum_e (alpha^[e] / rsum[e])^T u[e] in parts (fixed row ranges of the
+ * chunk, each part's tile stored whole -- no atomic adds), the parts are folded in ascending
+ * order into one NP x NP accumulator, chunks in stream order, and a_cnt = A o S is one product
+ * per entry: a_cnt is exactly 0 wherever A is 0.  pi_cnt adds the sequences' gamma_0 in one
+ * fixed order.  Results are therefore bit-identical between two calls with the same arguments
+ * on the same handle state and between the host and device variants; they are NOT bit-identical
+ * across chunk plans (workspace_bytes) or part sizes (tuning key xi_part_rows), which regroup
+ * the sums -- the bounds hold for all of them.
+ * Numerics, with u = 2^-53, T the longest sequence of the call, L its elements, B its sequences:
+ *   |a_cnt - exact|  <= (4 T (N + 8) + L + 8) u a_cnt + 1e-290 L,
+ *   |pi_cnt - exact| <= (4 T (N + 8) + B) u pi_cnt + 1e-290 B.
+ * 4 T (N + 8) u: the row bounds of cv_posterior_batch, 2 T (N + 8) u for each of alpha^ and
+ * beta^, cover numerator and normaliser of xi_t as they cover gamma's; + 8: the roundings of one
+ * term (the division, alpha^ times it, the emission product in u, the product with A, the
+ * matrix core's fused multiply-add); + L (B): a sum of non-negative terms gains at most one
+ * rounding per added term in whatever grouping (DESIGN.md "Expected counts").  Under dense
+ * emissions N + 8 reads N + 6 + c with c = 2, unchanged (the row scale 2^-k cancels in xi as in
+ * gamma).  Entries of A below 10^-290 are outside the contract: S = xi / A can leave the range.
+ * opts, limits and errors as for cv_posterior_batch: dtype CV_DTYPE_F64 (F32: CV_EUNSUPPORTED),
+ * assoc CV_ASSOC_VITERBI and kernel CV_KERNEL_AUTO or CV_KERNEL_GENERIC (others CV_EINVAL);
+ * forced, stream and workspace_bytes are honoured; N <= 4096 (above: CV_EUNSUPPORTED); the host
+ * variant returns CV_EINFEASIBLE, after writing every output, when a sequence is infeasible.
+ * Workspace: 2 * 8 NP + 8 bytes per element of a chunk (forward row, u row, 1 / rsum), plus
+ * 8 NP + 4 with dense emissions, plus the GEMM's partial tiles (8 NP^2 bytes per part; at most
+ * 512 MiB and at most half of workspace_bytes, at least one part), all under workspace_bytes
+ * (0: the posterior path's default); beside them 8 NP bytes per sequence (gamma_0) and one
+ * NP x NP accumulator.  A single sequence over the cap is CV_ENOMEM under dense emissions, as
+ * there.  cv_hmm_release_workspaces frees all of it.
+ * cv_last_timing: fwd_ms the forward pass (including staging), bt_ms the backward pass plus the
+ * count kernels; the rest as for cv_posterior_batch.  Host pointers; synchronous. */
+CV_API cv_status cv_expected_counts(cv_hmm* h, int64_t nseq, const int64_t* offsets, const int32_t* obs,
+                                    const cv_opts* opts, double* loglik_out /*[nseq]*/, double* pi_cnt_out /*[N]*/,
+                                    double* a_cnt_out /*[N*N] from-major*/, double* gamma_out /*nullable [L*N]*/,
+                                    uint8_t* status_out /*[nseq]*/);
+/* The same on device-resident buffers, with cv_posterior_batch_device's contract: enqueued on
+ * opts->stream (or the handle's stream), returns after enqueueing (CV_OK where the host variant
+ * reports CV_EINFEASIBLE: read status_dev); offsets_host (nullable) is a host copy of the
+ * offsets; opts->forced is a device pointer. */
+CV_API cv_status cv_expected_counts_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
+                                           const int64_t* offsets_dev, const int32_t* obs_dev, const cv_opts* opts,
+                                           double* loglik_dev, double* pi_cnt_dev, double* a_cnt_dev, double* gamma_dev,
+                                           uint8_t* status_dev);
+/* The same under caller-supplied emission scores, read as cv_posterior_emissions reads them
+ * (emis[e * ld + j], j < N <= ld; a NaN, +inf or |x| >= 2^40 makes its sequence CV_SEQ_BADOBS,
+ * which counts nothing).  ld < N or a null emis is CV_EINVAL. */
+CV_API cv_status cv_expected_counts_emissions(cv_hmm* h, int64_t nseq, const int64_t* offsets, const double* emis,
+                                              int64_t ld, const cv_opts* opts, double* loglik_out, double* pi_cnt_out,
+                                              double* a_cnt_out, double* gamma_out, uint8_t* status_out);
+CV_API cv_status cv_expected_counts_emissions_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
+                                                     const int64_t* offsets_dev, const double* emis_dev, int64_t ld,
+                                                     const cv_opts* opts, double* loglik_dev, double* pi_cnt_dev,
+                                                     double* a_cnt_dev, double* gamma_dev, uint8_t* status_dev);
 
 /* ---- trait Solver (viterbi_solver.rs:11-16) -------------------------------------------
  * kind: "gpu"      f32 trellis kernel, VITERBI association, f64 re-scored objective
