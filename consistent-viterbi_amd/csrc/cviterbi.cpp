@@ -344,6 +344,7 @@ struct cv_hmm {
   std::vector<int64_t> sort_pos;        // counting-sort buckets of the longest-first order
   // timing events of the last call
   std::vector<hipEvent_t> ev;  // 4 per chunk: fwd start/end (main stream), bt start/end
+  std::vector<uint8_t> ev_nobt;  // per chunk of ev: nothing ran between its bt events (bt_ms reads 0)
   int64_t last_launches = 0;
   size_t last_ev_base = 0;  // first event of the last call in ev
   // cv_timing_begin/end: every decode call's events kept (appended) until cv_timing_end
@@ -764,6 +765,10 @@ cv_status reserve_events(cv_hmm* h, bool side_ws, size_t nev, size_t* eb) {
   std::vector<hipEvent_t>& evv = side_ws ? h->side.ev : h->ev;
   for (size_t i = 0; i < nev; ++i)
     if (!get_event(evv, *eb + i)) return set_err(CV_EDEVICE, "hipEventCreate failed");
+  if (!side_ws) {
+    if (h->ev_nobt.size() < (*eb + nev + 3) / 4) h->ev_nobt.resize((*eb + nev + 3) / 4);
+    std::fill(h->ev_nobt.begin() + (ptrdiff_t)(*eb / 4), h->ev_nobt.begin() + (ptrdiff_t)((*eb + nev + 3) / 4), (uint8_t)0);
+  }
   return CV_OK;
 }
 
@@ -1482,6 +1487,12 @@ struct SampleReq {
 struct CountsReq {
   double* pi_cnt;  // device, [N]
   double* a_cnt;   // device, [N][N]
+  // cv_loglik_grad_emissions*: the gradient arm (grad.hip) -- every term times its sequence's weight,
+  // the gamma rows (then the gradient of E) at the caller's stride; gamma_dev is null in such a call
+  bool grad = false;
+  const double* weight = nullptr;  // device, [nseq]; null: all 1
+  double* egrad = nullptr;         // device, nullable, row e at egrad + e * ld_grad
+  int64_t ld_grad = 0;
 };
 
 // Core of cv_posterior_batch*: all pointers are device pointers except offsets_host.  Chunks of
@@ -1498,7 +1509,8 @@ struct CountsReq {
 // cnt (cv_expected_counts*): the backward pass runs with its counts arm (8 NP + 8 bytes per
 // element more: the U row and 1 / rsum), each chunk's rows then go through the count GEMM and its
 // fold into ps_xi_s (zeroed here), and the last chunk is followed by the kernels that write
-// pi_cnt and a_cnt -- all inside the chunk's backward events, so bt_ms covers them.
+// pi_cnt and a_cnt -- all inside the chunk's backward events, so bt_ms covers them.  With cnt->grad
+// (cv_loglik_grad_emissions*) the backward pass is the gradient arm's; nothing else differs.
 cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, const int64_t* offsets_dev,
                            const int32_t* obs_dev, const cv_opts& o, double* loglik_dev, int32_t* path_dev,
                            double* gamma_dev, uint8_t* status_dev, hipStream_t stream, const EmisSrc* emis = nullptr,
@@ -1597,6 +1609,8 @@ cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
   const size_t nev = 4 * chunks.size();
   size_t eb;
   if ((st = reserve_events(h, false, nev, &eb)) != CV_OK) return st;
+  // scoring mode: no backward launch, and cv_last_timing says so exactly (bt_ms = 0)
+  if (!store) std::fill(h->ev_nobt.begin() + (ptrdiff_t)(eb / 4), h->ev_nobt.begin() + (ptrdiff_t)(eb / 4 + chunks.size()), (uint8_t)1);
   for (size_t ci = 0; ci < chunks.size(); ++ci) {
     const auto& c = chunks[ci];
     cvp::PostArgs g{};
@@ -1624,6 +1638,9 @@ cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
       g.urows = ws_urows;
       g.inv = ws_inv;
       g.g0 = h->ps_g0.as<double>();
+      g.weight = cnt->weight;
+      g.egrad = cnt->egrad;
+      g.ld_grad = cnt->ld_grad;
     }
     hipEvent_t f0 = h->ev[eb + 4 * ci], f1 = h->ev[eb + 4 * ci + 1], b0 = h->ev[eb + 4 * ci + 2], b1 = h->ev[eb + 4 * ci + 3];
     HIP_TRY(hipEventRecord(f0, stream));
@@ -1694,7 +1711,7 @@ cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
       }
       if (err != hipSuccess) return set_err(CV_EDEVICE, "sampling launch failed: %s", hipGetErrorString(err));
     } else if (store) {
-      err = cvp::launch_post_bwd(g, generic, stream);
+      err = cnt && cnt->grad ? cvp::launch_post_grad_bwd(g, generic, stream) : cvp::launch_post_bwd(g, generic, stream);
       if (err != hipSuccess) return set_err(CV_EDEVICE, "posterior backward launch failed: %s", hipGetErrorString(err));
     }
     if (cnt) {
@@ -2980,6 +2997,92 @@ CV_API cv_status cv_expected_counts_emissions(cv_hmm* h, int64_t nseq, const int
                                               double* a_cnt_out, double* gamma_out, uint8_t* status_out) {
   return counts_host_entry(h, nseq, offsets, nullptr, emis, ld, true, opts, loglik_out, pi_cnt_out, a_cnt_out, gamma_out,
                            status_out);
+}
+
+// ---- likelihood gradients under emission scores: cv_loglik_grad_emissions* ---------------------
+// The dense expected-counts entries with the gradient request: per-sequence weights (null: all 1)
+// and the gradient rows of E at the caller's stride in place of gamma.
+CV_API cv_status cv_loglik_grad_emissions_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
+                                                 const int64_t* offsets_dev, const double* emis_dev, int64_t ld,
+                                                 const double* weight_dev, const cv_opts* opts, double* loglik_dev,
+                                                 double* pi_grad_dev, double* a_grad_dev, double* emis_grad_dev,
+                                                 int64_t ld_grad, uint8_t* status_dev) {
+  if (!h) return set_err(CV_EINVAL, "null handle");
+  if (nseq < 0) return set_err(CV_EINVAL, "nseq < 0");
+  if (!pi_grad_dev || !a_grad_dev) return set_err(CV_EINVAL, "null device buffer");
+  if (nseq > 0 && (!offsets_dev || !emis_dev || !loglik_dev || !status_dev)) return set_err(CV_EINVAL, "null device buffer");
+  if (emis_grad_dev && ld_grad < h->N)
+    return set_err(CV_EINVAL, "ld_grad = %lld is less than N = %d", (long long)ld_grad, h->N);
+  const cv_opts o = opts ? *opts : default_opts();
+  cv_status st = posterior_emissions_args_ok(h, ld, o);
+  if (st != CV_OK) return st;
+  CV_LOCK(h);
+  if ((st = set_device(h)) != CV_OK) return st;
+  hipStream_t stream = o.stream ? (hipStream_t)o.stream : h->stream;
+  const EmisSrc src{emis_dev, ld};
+  CountsReq cnt{pi_grad_dev, a_grad_dev};
+  cnt.grad = true;
+  cnt.weight = weight_dev;
+  cnt.egrad = emis_grad_dev;
+  cnt.ld_grad = ld_grad;
+  return posterior_device(h, nseq, offsets_host, offsets_dev, nullptr, o, loglik_dev, nullptr, nullptr, status_dev, stream,
+                          &src, nullptr, &cnt);
+}
+
+// Host arrays: the weights ride behind pi_grad and a_grad in st_cnt; the gradient rows are staged
+// compact in st_gamma and copied back at the caller's stride (its columns beyond N stay untouched).
+CV_API cv_status cv_loglik_grad_emissions(cv_hmm* h, int64_t nseq, const int64_t* offsets, const double* emis, int64_t ld,
+                                          const double* weight, const cv_opts* opts, double* loglik_out,
+                                          double* pi_grad_out, double* a_grad_out, double* emis_grad_out,
+                                          int64_t ld_grad, uint8_t* status_out) {
+  if (!h) return set_err(CV_EINVAL, "null handle");
+  if (nseq < 0 || !pi_grad_out || !a_grad_out) return set_err(CV_EINVAL, "null argument");
+  if (nseq > 0 && (!offsets || !emis || !loglik_out || !status_out)) return set_err(CV_EINVAL, "null argument");
+  if (emis_grad_out && ld_grad < h->N)
+    return set_err(CV_EINVAL, "ld_grad = %lld is less than N = %d", (long long)ld_grad, h->N);
+  cv_opts o = opts ? *opts : default_opts();
+  cv_status st = posterior_emissions_args_ok(h, ld, o);
+  if (st != CV_OK) return st;
+  CV_LOCK(h);
+  if ((st = set_device(h)) != CV_OK) return st;
+  const size_t N = (size_t)h->N;
+  if (nseq == 0) {  // overwritten, not accumulated
+    std::fill(pi_grad_out, pi_grad_out + N, 0.0);
+    std::fill(a_grad_out, a_grad_out + N * N, 0.0);
+    return CV_OK;
+  }
+  HostBatch hb{h, nseq, offsets, nullptr, o.stream ? (hipStream_t)o.stream : h->stream};
+  if ((st = hb.stage(o, 0, 1)) != CV_OK) return st;
+  if (emis_grad_out && (st = h->st_gamma.ensure(hb.plane() * N * 8)) != CV_OK) return st;
+  if ((st = h->st_cnt.ensure((N + N * N + (weight ? (size_t)nseq : 0)) * 8)) != CV_OK) return st;
+  EmisSrc src{};
+  if ((st = hb.stage_emis(emis, ld, &src)) != CV_OK) return st;
+  CountsReq cnt{h->st_cnt.as<double>(), h->st_cnt.as<double>() + N};
+  cnt.grad = true;
+  if (weight) {
+    double* const wd = h->st_cnt.as<double>() + N + N * N;
+    HIP_TRY(hipMemcpyAsync(wd, weight, (size_t)nseq * 8, hipMemcpyHostToDevice, hb.stream));
+    cnt.weight = wd;
+  }
+  cnt.egrad = emis_grad_out ? h->st_gamma.as<double>() : nullptr;
+  cnt.ld_grad = (int64_t)N;
+  st = posterior_device(h, nseq, offsets, h->st_off.as<int64_t>(), nullptr, o, h->st_score.as<double>(), nullptr, nullptr,
+                        h->st_status.as<uint8_t>(), hb.stream, &src, nullptr, &cnt);
+  if (st != CV_OK) return hb.fail(st);
+  const size_t rows = (size_t)(hb.total - hb.base);
+  if (emis_grad_out && rows && hb.err == hipSuccess)
+    hb.err = hipMemcpy2DAsync(emis_grad_out + (size_t)hb.base * (size_t)ld_grad, (size_t)ld_grad * 8,
+                              h->st_gamma.as<double>() + (size_t)hb.base * N, N * 8, N * 8, rows, hipMemcpyDeviceToHost,
+                              hb.stream);
+  hb.fetch_seqs(loglik_out, h->st_score);
+  hb.fetch_seqs(status_out, h->st_status);
+  if (hb.err == hipSuccess) hb.err = hipMemcpyAsync(pi_grad_out, cnt.pi_cnt, N * 8, hipMemcpyDeviceToHost, hb.stream);
+  if (hb.err == hipSuccess) hb.err = hipMemcpyAsync(a_grad_out, cnt.a_cnt, N * N * 8, hipMemcpyDeviceToHost, hb.stream);
+  if ((st = hb.finish()) != CV_OK) return st;
+  for (int64_t s = 0; s < nseq; ++s)
+    if (status_out[s] == CV_SEQ_INFEASIBLE)
+      return set_err(CV_EINFEASIBLE, "sequence %lld has likelihood 0", (long long)s);
+  return CV_OK;
 }
 
 // ---- consistency-constrained decode --------------------------------------------------------
@@ -4357,6 +4460,7 @@ cv_status sum_timing(cv_hmm* h, size_t eb, int64_t launches, cv_timing* out) {
     float f = 0, b = 0;
     HIP_TRY(hipEventElapsedTime(&f, h->ev[eb + 4 * c], h->ev[eb + 4 * c + 1]));
     HIP_TRY(hipEventElapsedTime(&b, h->ev[eb + 4 * c + 2], h->ev[eb + 4 * c + 3]));
+    if (eb / 4 + (size_t)c < h->ev_nobt.size() && h->ev_nobt[eb / 4 + (size_t)c]) b = 0;
     out->fwd_ms += f;
     out->bt_ms += b;
   }

@@ -1,7 +1,8 @@
 // post_bwd.h -- the backward pass of the sum-product kernels, shared by posterior.hip (post_bwd_mm,
-// post_bwd_gen: path and gamma) and counts.hip (post_cnt_bwd_mm, post_cnt_bwd_gen: the same pass
-// with the counts arm of cv_expected_counts*).  One body each, inlined into its kernels; the
-// layouts are described in posterior.hip.
+// post_bwd_gen: path and gamma), counts.hip (post_cnt_bwd_mm, post_cnt_bwd_gen: the same pass
+// with the counts arm of cv_expected_counts*) and grad.hip (post_grad_bwd_mm, post_grad_bwd_gen:
+// the counts arm under per-sequence weights, cv_loglik_grad_emissions*).  One body each, inlined
+// into its kernels; the layouts are described in posterior.hip.
 #ifndef CV_KERNELS_POST_BWD_H
 #define CV_KERNELS_POST_BWD_H
 
@@ -71,8 +72,18 @@ __device__ __forceinline__ void post_setup(const PostArgs& g, int64_t* s_seq, in
 // COUNTS (cv_expected_counts*, the kernel post_cnt_bwd_mm): the operand u_{t+1} also goes to row
 // t of g.urows as it is written to LDS, 1 / rsum_t to g.inv, and gamma_0 to the sequence's slot
 // of g.g0.  One body, inlined into both kernels.
-template <int NP, int MT, int WV, bool GAMMA, bool COUNTS>
+// GRAD (cv_loglik_grad_emissions*, the kernel post_grad_bwd_mm; with COUNTS): inv, gamma_0 and the
+// gamma rows carry the sequence's weight w_s as one more product after the division, behind the
+// same selects (a sequence that is not OK stores zeros whatever its weight holds), and the rows go
+// to g.egrad at the caller's stride g.ld_grad in place of g.gamma.
+template <int G>
+__device__ __forceinline__ double* grad_weights() {  // LDS of the kernels with the GRAD arm only
+  __shared__ double s_w[G];
+  return s_w;
+}
+template <int NP, int MT, int WV, bool GAMMA, bool COUNTS, bool GRAD = false>
 __device__ __forceinline__ void bwd_mm_body(const PostArgs g) {
+  static_assert(COUNTS || !GRAD, "the gradient arm extends the counts arm");
   constexpr int CT = NP / (16 * WV), G = 16 * MT;
   __shared__ __attribute__((aligned(16))) double xt[NP * (G + 1)];
   __shared__ double redm[WV][G], reds[WV][G], redv[WV][G];
@@ -85,6 +96,11 @@ __device__ __forceinline__ void bwd_mm_body(const PostArgs g) {
   double* const dump = g.dump + (size_t)((blockIdx.x * WV + w) & (kPostDumpWaves - 1)) * 64 + l;
   post_setup<G>(g, s_seq, s_e0, s_r0, s_T, &s_tmax);
   if (tid < G) s_ok[tid] = s_seq[tid] >= 0 && g.status[s_seq[tid]] == kSeqOk;
+  double* s_w = nullptr;
+  if constexpr (GRAD) {
+    s_w = grad_weights<G>();
+    if (tid < G) s_w[tid] = (g.weight && s_seq[tid] >= 0) ? g.weight[s_seq[tid]] : 1.0;
+  }
   const int tmax = s_tmax;
   if (tmax <= 0) return;  // workgroup-uniform
   auto fetch = [&](int r) {  // observation and forced state of step r (element T - 1 - r)
@@ -185,7 +201,24 @@ __device__ __forceinline__ void bwd_mm_body(const PostArgs g) {
           }
           g.path[el] = rsum > 0.0 ? bi : -1;
         }
-        if (GAMMA) {
+        if constexpr (GRAD) {
+          const double ws = s_w[gi];
+          if (GAMMA) {  // the gradient row of E, straight into the caller's array
+            double* grow = g.egrad + (size_t)el * (size_t)g.ld_grad;
+#pragma unroll
+            for (int n = 0; n < CT; ++n) {
+              const double gm = rsum > 0.0 ? (al[m][q][n] / rsum) * ws : 0.0;
+              *((on && col[n] < N) ? grow + col[n] : dump) = gm;
+            }
+          }
+          if (w == 0 && cl == 0 && on) g.inv[s_r0[gi] + t] = (r > 0 && rsum > 0.0) ? (1.0 / rsum) * ws : 0.0;
+          double* zrow = g.g0 + (size_t)max(s_seq[gi], (int64_t)0) * NP;
+#pragma unroll
+          for (int n = 0; n < CT; ++n) {
+            const double gm = rsum > 0.0 ? (al[m][q][n] / rsum) * ws : 0.0;
+            *(t == 0 ? zrow + col[n] : dump) = gm;
+          }
+        } else if (GAMMA) {
           double* grow = g.gamma + (size_t)el * N;
 #pragma unroll
           for (int n = 0; n < CT; ++n) {
@@ -193,7 +226,7 @@ __device__ __forceinline__ void bwd_mm_body(const PostArgs g) {
             *((on && col[n] < N) ? grow + col[n] : dump) = gm;
           }
         }
-        if constexpr (COUNTS) {
+        if constexpr (COUNTS && !GRAD) {
           // rsum_t = 0 in a sequence that is not OK (live) and where the tags leave no path
           if (w == 0 && cl == 0 && on) g.inv[s_r0[gi] + t] = (r > 0 && rsum > 0.0) ? 1.0 / rsum : 0.0;
           double* zrow = g.g0 + (size_t)max(s_seq[gi], (int64_t)0) * NP;
@@ -257,9 +290,11 @@ __device__ __forceinline__ double dot_col(const double* __restrict__ x, const do
   return s;
 }
 
-// The backward pass of the plain kernels (post_bwd_gen; COUNTS: post_cnt_bwd_gen, as in bwd_mm_body)
-template <bool COUNTS>
+// The backward pass of the plain kernels (post_bwd_gen; COUNTS: post_cnt_bwd_gen, GRAD:
+// post_grad_bwd_gen, both as in bwd_mm_body)
+template <bool COUNTS, bool GRAD = false>
 __device__ __forceinline__ void bwd_gen_body(const PostArgs g) {
+  static_assert(COUNTS || !GRAD, "the gradient arm extends the counts arm");
   extern __shared__ double sm[];
   __shared__ double red[4];
   __shared__ int redi[4];
@@ -271,6 +306,8 @@ __device__ __forceinline__ void bwd_gen_body(const PostArgs g) {
   const int64_t e0 = g.offsets[s];
   const int T = (int)(g.offsets[s + 1] - e0);
   const bool ok = g.status[s] == kSeqOk;
+  double ws = 1.0;
+  if constexpr (GRAD) ws = g.weight ? g.weight[s] : 1.0;
   for (int t = T - 1; t >= 0; --t) {
     const double* arow = g.rows + (size_t)(e0 - g.elem_base + t) * NP;
     double vm = 0.0, vs = 0.0, bv = -1.0;
@@ -291,8 +328,11 @@ __device__ __forceinline__ void bwd_gen_body(const PostArgs g) {
     block_argmax(bv, bi, red, redi);
     const int e = row_exp(rmax);
     if (g.path && tid == 0) g.path[e0 + t] = rsum > 0.0 ? bi : -1;
-    if constexpr (COUNTS)
+    if constexpr (GRAD) {
+      if (tid == 0) g.inv[e0 - g.elem_base + t] = (t < T - 1 && rsum > 0.0) ? (1.0 / rsum) * ws : 0.0;
+    } else if constexpr (COUNTS) {
       if (tid == 0) g.inv[e0 - g.elem_base + t] = (t < T - 1 && rsum > 0.0) ? 1.0 / rsum : 0.0;
+    }
     int o = g.obs[e0 + t];
     o = (o < 0 || o >= g.nobs) ? 0 : o;
     const int fc = g.forced ? g.forced[e0 + t] : -1;
@@ -300,10 +340,18 @@ __device__ __forceinline__ void bwd_gen_body(const PostArgs g) {
     __syncthreads();  // block_argmax's slots read by every thread
     for (int j = tid; j < NP; j += 256) {
       const double W = y[j];
-      if (g.gamma && j < N) g.gamma[(size_t)(e0 + t) * N + j] = rsum > 0.0 ? (ok ? arow[j] * W : 0.0) / rsum : 0.0;
+      if constexpr (GRAD) {  // the gradient row of E, straight into the caller's array
+        if (g.egrad && j < N)
+          g.egrad[(size_t)(e0 + t) * (size_t)g.ld_grad + j] = rsum > 0.0 ? ((ok ? arow[j] * W : 0.0) / rsum) * ws : 0.0;
+      } else {
+        if (g.gamma && j < N) g.gamma[(size_t)(e0 + t) * N + j] = rsum > 0.0 ? (ok ? arow[j] * W : 0.0) / rsum : 0.0;
+      }
       const double u = ldexp(W, -e) * er[j];
       x[j] = (fc < 0 || fc == j) ? u : 0.0;
-      if constexpr (COUNTS) {
+      if constexpr (GRAD) {
+        if (t > 0) g.urows[(size_t)(e0 - g.elem_base + t - 1) * NP + j] = x[j];
+        else g.g0[(size_t)s * NP + j] = rsum > 0.0 ? ((ok ? arow[j] * W : 0.0) / rsum) * ws : 0.0;
+      } else if constexpr (COUNTS) {
         if (t > 0) g.urows[(size_t)(e0 - g.elem_base + t - 1) * NP + j] = x[j];
         else g.g0[(size_t)s * NP + j] = rsum > 0.0 ? (ok ? arow[j] * W : 0.0) / rsum : 0.0;
       }

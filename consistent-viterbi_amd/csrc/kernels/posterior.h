@@ -1,5 +1,5 @@
 // posterior.h -- argument block and launchers of the sum-product (forward-backward) kernels
-// (posterior.hip) and of the expected-counts kernels behind them (counts.hip).  Internal to libcviterbi; the public boundary is include/cviterbi.h
+// (posterior.hip) and of the expected-counts and gradient kernels behind them (counts.hip, grad.hip).  Internal to libcviterbi; the public boundary is include/cviterbi.h
 // (cv_posterior_batch*).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -43,6 +43,11 @@ struct PostArgs {
   double* urows;  // [elements][NP] u_{t+1} = b(o_{t+1}) o mask_{t+1} o beta^_{t+1}; unwritten at t = T - 1
   double* inv;    // [elements] 1 / rsum_t; 0 at t = T - 1, where rsum_t = 0, and in a sequence that is not OK
   double* g0;     // [nseq][NP] gamma_0 of every OK sequence (the other slots stay unwritten)
+  // gradient arm of the counts arm (cv_loglik_grad_emissions*, grad.hip; read by its kernels only):
+  // inv, g0 and the gamma rows carry the factor weight[s], and the rows go to egrad, not gamma
+  const double* weight;  // nullable, [nseq]: all 1
+  double* egrad;         // nullable, row e at egrad + e * ld_grad, N values; the columns beyond stay unwritten
+  int64_t ld_grad;       // >= N
 };
 
 // ---- expected transition counts (cv_expected_counts*) ----------------------------------------
@@ -88,6 +93,8 @@ hipError_t launch_post_fwd(const PostArgs& g, bool generic, hipStream_t stream);
 hipError_t launch_post_bwd(const PostArgs& g, bool generic, hipStream_t stream);
 // the backward pass with the counts arm (g.urows, g.inv, g.g0 set; launch_post_bwd forwards here)
 hipError_t launch_post_cnt_bwd(const PostArgs& g, bool generic, hipStream_t stream);
+// the counts arm with the gradient arm (g.weight, g.egrad, g.ld_grad read): grad.hip
+hipError_t launch_post_grad_bwd(const PostArgs& g, bool generic, hipStream_t stream);
 // S += R^T U over the chunk's rows (R = alpha^ o inv): post_xi_gemm, then post_xi_fold
 hipError_t launch_post_xi(const XiArgs& x, hipStream_t stream);
 // after the last chunk: a_cnt and pi_cnt

@@ -11,6 +11,8 @@ from .decode import (constrained_pairs, constrained_partials, constrained_select
 from .counts import (expected_counts, expected_counts_device, expected_counts_emissions,  # noqa: F401
                      expected_counts_emissions_device, reestimate)
 from .emissions import decode_emissions, decode_emissions_device  # noqa: F401
+from .grad import loglik_grad_emissions, loglik_grad_emissions_device  # noqa: F401
+from . import autograd  # noqa: F401
 from .emissions import posterior_emissions, posterior_emissions_device, score_emissions  # noqa: F401
 from .fit import fit_mle, fit_train, last_fit_stats  # noqa: F401
 from .kbest import kbest_batch, kbest_batch_device  # noqa: F401

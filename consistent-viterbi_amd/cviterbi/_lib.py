@@ -48,6 +48,7 @@ EXPORTS = [
     "cv_posterior_emissions", "cv_posterior_emissions_device",
     "cv_expected_counts", "cv_expected_counts_device",
     "cv_expected_counts_emissions", "cv_expected_counts_emissions_device",
+    "cv_loglik_grad_emissions", "cv_loglik_grad_emissions_device",
     "cv_sample_batch", "cv_sample_batch_device",
     "cv_last_t64_stats", "cv_last_fixed_first_stats", "cv_hmm_fit_last_stats",
     "cv_last_first_pass_kind", "cv_f32ru_trace",
@@ -142,6 +143,8 @@ def lib():
         "cv_expected_counts_device": ([P, I64, P, P, P, P, P, P, P, P, P], S),
         "cv_expected_counts_emissions": ([P, I64, P, P, I64, P, P, P, P, P, P], S),
         "cv_expected_counts_emissions_device": ([P, I64, P, P, P, I64, P, P, P, P, P, P], S),
+        "cv_loglik_grad_emissions": ([P, I64, P, P, I64, P, P, P, P, P, P, I64, P], S),
+        "cv_loglik_grad_emissions_device": ([P, I64, P, P, P, I64, P, P, P, P, P, P, I64, P], S),
         "cv_last_timing": ([P, P], S),
         "cv_timing_begin": ([P], S),
         "cv_timing_end": ([P, P], S),

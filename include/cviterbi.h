@@ -761,6 +761,58 @@ CV_API cv_status cv_expected_counts_emissions_device(cv_hmm* h, int64_t nseq, co
                                                      const cv_opts* opts, double* loglik_dev, double* pi_cnt_dev,
                                                      double* a_cnt_dev, double* gamma_dev, uint8_t* status_dev);
 
+/* ---- likelihood gradients under emission scores (autograd's backward pass) ---------------------
+ * The gradient of  F = sum_s w_s log10 P(o_s | model, tags)  over the sequences with status
+ * CV_SEQ_OK, in log10 units on both sides (F in log10, the parameters as the handle and emis hold
+ * them, log10):
+ *   emis_grad_out[e * ld_grad + j] = dF / d emis[e][j]     = w_s gamma_e[j]            (j < N),
+ *   pi_grad_out[i]                 = dF / d log10 pi[i]    = sum_s w_s gamma_0(s)[i],
+ *   a_grad_out[i * N + j]          = dF / d log10 A[i][j]  = sum_s w_s sum_t xi_t(s)(i, j).
+ * This is cv_expected_counts_emissions with a weight per sequence, and everything that entry
+ * promises holds here too: how the model and emis are read, the statuses, opts and their errors,
+ * N <= 4096, chunking under workspace_bytes and its sizes, the tuning key xi_part_rows,
+ * cv_last_timing, release by cv_hmm_release_workspaces, no atomic adds and the bit-identity of
+ * repeated calls and of the host and device variants.  loglik_out and status_out are that
+ * entry's bit for bit.  weight null means all 1; with weight null or all 1.0, pi_grad_out,
+ * a_grad_out and emis_grad_out (at ld_grad = N) are bit-identical to its pi_cnt_out, a_cnt_out and
+ * gamma_out: the weight enters as one product after the division (1 / rsum_t) w_s, gamma w_s.
+ * a_grad is exactly 0 wherever A is 0, pi_grad wherever pi is 0, emis_grad wherever the score is
+ * -inf or a tag excludes the state.  Outputs are overwritten, not accumulated (nseq = 0 writes
+ * zeros to pi_grad and a_grad).
+ * emis_grad_out (nullable): N values per element at row stride ld_grad >= N (ld_grad < N with a
+ * non-null emis_grad_out is CV_EINVAL); the columns [N, ld_grad) are never written; rows need
+ * 8-byte alignment only.  The rows of sequences that are not CV_SEQ_OK are written as zeros, and
+ * such sequences contribute nothing to pi_grad and a_grad WHATEVER their weight holds (a select
+ * on the status, not a product with 0: NaN and inf weights are harmless there).  An OK sequence
+ * with a non-finite weight makes every output it touches non-finite: its emis_grad rows, and the
+ * entries of pi_grad and a_grad (possibly all of them).  An OK sequence with weight 0 adds only
+ * +-0 terms.  A null pi_grad_out or a_grad_out is CV_EINVAL, as are the null pointers and ld < N
+ * that cv_expected_counts_emissions rejects.
+ * Numerics, with u = 2^-53, T the longest sequence of the call, L its elements, B its sequences,
+ * and X_abs the same statistic computed with |w_s| in place of w_s:
+ *   |a_grad - exact|           <= (4 T (N + 8) + L + 9) u a_abs + 1e-290 L,
+ *   |pi_grad - exact|          <= (4 T (N + 8) + B + 1) u pi_abs + 1e-290 B,
+ *   |emis_grad[e][j] - w_s gamma| <= (4 T (N + 8) + 1) u |w_s| gamma + 1e-290 max(1, |w_s|).
+ * These are the bounds of cv_expected_counts* with one more rounding per term (the product with
+ * the weight) and, the terms now being signed, each sum of n terms gaining at most (n - 1) u of
+ * the sum of their magnitudes (DESIGN.md "Likelihood gradients").  N + 8 reads N + 6 + c, c = 2,
+ * as there.  Host pointers; synchronous; CV_EINFEASIBLE after writing every output, as there. */
+CV_API cv_status cv_loglik_grad_emissions(cv_hmm* h, int64_t nseq, const int64_t* offsets, const double* emis, int64_t ld,
+                                          const double* weight /*[nseq], nullable = all 1*/, const cv_opts* opts,
+                                          double* loglik_out /*[nseq]*/, double* pi_grad_out /*[N]*/,
+                                          double* a_grad_out /*[N*N] from-major*/,
+                                          double* emis_grad_out /*nullable, [L][ld_grad]*/, int64_t ld_grad,
+                                          uint8_t* status_out /*[nseq]*/);
+/* The same on device-resident buffers, with cv_expected_counts_emissions_device's contract:
+ * enqueued on opts->stream (or the handle's stream), returns after enqueueing; weight_dev
+ * (nullable) and emis_grad_dev (nullable) are device pointers.  This is the backward pass of
+ * cviterbi.autograd.sequence_loglik with weight_dev = grad_output. */
+CV_API cv_status cv_loglik_grad_emissions_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
+                                                 const int64_t* offsets_dev, const double* emis_dev, int64_t ld,
+                                                 const double* weight_dev, const cv_opts* opts, double* loglik_dev,
+                                                 double* pi_grad_dev, double* a_grad_dev, double* emis_grad_dev,
+                                                 int64_t ld_grad, uint8_t* status_dev);
+
 /* ---- trait Solver (viterbi_solver.rs:11-16) -------------------------------------------
  * kind: "gpu"      f32 trellis kernel, VITERBI association, f64 re-scored objective
  *       "gpu-f64"  f64, VITERBI association (reference numerics, row A0)
