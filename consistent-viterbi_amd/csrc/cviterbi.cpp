@@ -4509,19 +4509,32 @@ CV_API int32_t cv_last_first_pass_kind(const cv_hmm* h) {
 // everything they store copied out: what tests compare with the numpy model bit for bit.
 CV_API cv_status cv_f32ru_trace(cv_hmm* h, int64_t nseq, int64_t T, const int32_t* obs, float* rows, float* mu,
                                 float* r, float* e_last, int32_t* path) {
-  if (!h || !obs || !rows || !mu || !r || !e_last || !path) return set_err(CV_EINVAL, "null argument");
   if (nseq < 2 || T < 1 || nseq * T > (1 << 22)) return set_err(CV_EINVAL, "bad batch shape");
+  std::vector<int64_t> off((size_t)nseq + 1);
+  for (int64_t s = 0; s <= nseq; ++s) off[(size_t)s] = s * T;
+  return cv_f32ru_trace_ragged(h, nseq, off.data(), obs, rows, mu, r, e_last, path);
+}
+
+// The same on sequences of several lengths: sequences 2k and 2k + 1 are a pair and have one length.
+CV_API cv_status cv_f32ru_trace_ragged(cv_hmm* h, int64_t nseq, const int64_t* offsets, const int32_t* obs,
+                                       float* rows, float* mu, float* r, float* e_last, int32_t* path) {
+  if (!h || !offsets || !obs || !rows || !mu || !r || !e_last || !path) return set_err(CV_EINVAL, "null argument");
+  if (nseq < 2 || nseq > (1 << 22) || offsets[0] != 0) return set_err(CV_EINVAL, "bad batch shape");
+  for (int64_t s = 0; s < nseq; ++s) {
+    const int64_t len = offsets[s + 1] - offsets[s];
+    if (len < 1 || offsets[s + 1] > (1 << 22)) return set_err(CV_EINVAL, "bad batch shape");
+    if ((s & 1) && len != offsets[s] - offsets[s - 1]) return set_err(CV_EINVAL, "a pair of two lengths");
+  }
   CV_LOCK(h);
   cv_status st = set_device(h);
   if (st != CV_OK) return st;
-  for (int64_t e = 0; e < nseq * T; ++e)
+  const size_t ne = (size_t)offsets[nseq];
+  for (size_t e = 0; e < ne; ++e)
     if (obs[e] < 0 || obs[e] >= h->V) return set_err(CV_EINVAL, "observation out of range");
   if ((st = ensure_ru_tables(h)) != CV_OK) return st;
   if (h->ru_state != 1) return set_err(CV_EINVAL, "the model is outside the round-up pass's range");
   const int np = cvk::trellis_padded_states(h->N);
-  const size_t ne = (size_t)(nseq * T);
-  std::vector<int64_t> off((size_t)nseq + 1);
-  for (int64_t s = 0; s <= nseq; ++s) off[(size_t)s] = s * T;
+  const std::vector<int64_t> off(offsets, offsets + nseq + 1);
   DevBuf d_off, d_obs, d_rows, d_mu, d_r, d_e, d_path, d_cert;
   if ((st = upload(d_off, off.data(), off.size() * 8)) != CV_OK) return st;
   if ((st = upload(d_obs, obs, ne * 4)) != CV_OK) return st;

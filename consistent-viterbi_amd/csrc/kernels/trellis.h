@@ -173,6 +173,8 @@ struct RuScoreArgs {
   double* score;           // written with status OK where cert stays 1
   uint8_t* status;
 };
+// the K of trellis_fwd2_f32ru<NP, K> that the tuning key t64_f32ru_mu_every selects
+int ru_mu_every();
 hipError_t launch_ru_fwd2(int np, const RuFwdArgs& fa, int64_t npairs, hipStream_t stream);
 hipError_t launch_ru_bt(int np, const RuBtArgs& ba, hipStream_t stream, int lds_reserve = 0);
 hipError_t launch_ru_score(const RuScoreArgs& r, hipStream_t stream, int lds_reserve = 0);

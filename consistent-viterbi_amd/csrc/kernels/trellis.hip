@@ -34,6 +34,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "trellis.h"
 #include "../tuning.h"
@@ -1274,8 +1275,11 @@ hipError_t launch_fix_score(const FixScoreArgs& r, hipStream_t stream, int lds_r
 // bound of the real recurrence; the certificate (ru_score_f64) compares the exact f64 fold along
 // the candidate path with those bounds.
 //   trellis_fwd2_f32ru  trellis_fwd2_f32's layout and mix (one v_add_f32 and half a v_max3_f32 per
-//                       pair, one barrier per step) with trellis_fwd2_i32's row shift: row t is
-//                       stored minus mu_t, the maximum of row t-1.
+//                       pair, one barrier per step); row t is stored minus a shift mu_t that is
+//                       folded into the emission term ahead of the reduction.  The shift is a
+//                       per-sequence prediction dhat of the drift per step; the row maximum (as in
+//                       trellis_fwd2_i32) is taken at every K-th step only, where it corrects the
+//                       row and the prediction.
 //   backtrack_f32ru     one wave per sequence: first argmax w and r_t, the largest other candidate,
 //                       at every step, and E beside the terminal winner.
 //   ru_score_f64        one lane per sequence, default rounding: the f64 fold and the certificate.
@@ -1293,14 +1297,15 @@ __device__ __forceinline__ float dpp_max_half_mirror(float x) {
   return x;
 }
 
-template <int NP>
+template <int NP, int K>
 __global__ __launch_bounds__(NP * 4) void trellis_fwd2_f32ru(RuFwdArgs args) {
+  static_assert(K >= 1 && (K & (K - 1)) == 0, "the predictor divides by K exactly");
   using G = TrellisGeom<NP>;
   constexpr int R = G::R;
   constexpr int S = G::S;
   static_assert(R % 8 == 0, "pair kernel needs NP % 64 == 0");
   __shared__ __attribute__((aligned(16))) float lds[2][2][G::LDS_FLOATS];  // [X/Y][buffer]
-  __shared__ float mu[2][3];  // [X/Y][t % 3]: the maximum of row t
+  __shared__ float mu[2][3];  // [X/Y][q % 3]: the maximum of the row that measured step 1 + K q reads
   round_f32_up();
 
   const int lane = threadIdx.x & 63;
@@ -1378,7 +1383,7 @@ __global__ __launch_bounds__(NP * 4) void trellis_fwd2_f32ru(RuFwdArgs args) {
     lds[1][0][lds_w] = dy;
     dX[jw] = dx;
     dY[jw] = dy;
-    post_max(dx, &mu[0][0]);
+    post_max(dx, &mu[0][0]);  // block 0's slot
     post_max(dy, &mu[1][0]);
   }
   float eYr;
@@ -1394,15 +1399,33 @@ __global__ __launch_bounds__(NP * 4) void trellis_fwd2_f32ru(RuFwdArgs args) {
   ld8(&lds[0][0][rg * S], P);
 
   // One half-step at step t (trellis_fwd2_f32's ONEBAR form: the barrier follows the X half).
-  // mus = this sequence's mu slots, mrow = its shifts in memory.
-  auto half = [&](const float* dsrc, const float* nsrc, float* ldst, float* drow, float* mus, float* mrow, int t,
-                  const float& e_use, float& e_load, unsigned& o_load, bool first, int t_obs) {
+  // mus = this sequence's mu slots, mrow = its shifts in memory, dhat = its predicted drift per
+  // step (the same in every lane).  A measured half-step (meas) reads the maximum of row t-1 from
+  // slot sr and resets slot sr + 2; a posting one (post, the same in every wave) leaves row t's
+  // maximum in slot sr + 1.  Any other issues nothing for the shift but the one subtraction.
+  auto half = [&](const float* dsrc, const float* nsrc, float* ldst, float*& drow, float* mus, float* mrow, int t,
+                  const float& e_use, float& e_load, unsigned& o_load, float& dhat, int sr, auto first_c,
+                  bool meas, bool post, int t_obs) {
+    constexpr bool first = decltype(first_c)::value;
     e_load = et_row(o_load);
-    // the maximum of row t-1; a row of -inf alone (an infeasible prefix) shifts by -FLT_MAX, which
-    // keeps it -inf without a NaN
-    const float mu_use = fmaxf(mus[(t + 2) % 3], -__FLT_MAX__);
-    if (threadIdx.x == 0) mus[(t + 1) % 3] = ninf_f();
     if (KB > 1) ld8(dsrc + 8, Q);
+    // the shift of this row.  One region under the one flag: the compiler then keeps a single copy
+    // of the half-step body.
+    float mu_use = dhat;
+    if (meas) {
+      // a row of -inf alone (an infeasible prefix) counts -2^126: b'' - mu stays finite under RU
+      // and the row stays -inf without a NaN
+      const float m_raw = fmaxf(mus[sr], -0x1p126f);
+      if (threadIdx.x == 0) mus[sr == 0 ? 2 : sr - 1] = ninf_f();
+      // m_raw / K is exact (a tiny maximum counts 0: no scaling into the subnormal range); the
+      // first measured step sees row 0's offset, not a drift
+      const float d = dhat + (t > 1 && fabsf(m_raw) >= 0x1p-64f ? m_raw * (1.0f / K) : 0.0f);
+      // 0 also where d is not finite; every lane holds the same value: a scalar register
+      dhat = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(
+                                           __builtin_bit_cast(int, fabsf(d) < 64.0f ? d : 0.0f)));
+      mu_use = m_raw + dhat;
+    }
+    float emu = 0.0f;
     float m0a = ninf_f(), m0b = ninf_f(), m1a = ninf_f(), m1b = ninf_f();
     auto rows4 = [&](const float4& dd, int k, bool init) {
       const float s00 = dd.x + a_reg[2 * k + 0], s01 = dd.x + a_reg[2 * k + 1];
@@ -1432,34 +1455,50 @@ __global__ __launch_bounds__(NP * 4) void trellis_fwd2_f32ru(RuFwdArgs args) {
       else if (!(k & 1) && (k + 2 == KB || k + 1 == KB) && !first)
         ld8(nsrc, P);  // next half-step's block 0
       __builtin_amdgcn_sched_barrier(0);
+      if (k == (KB > 1 ? 1 : 0)) {
+        // folded into the emission term here, where the subtraction issues beside the adds (the
+        // emission row was loaded a half-step ago).  Every lane stores the shift, one dword per
+        // sequence and step, as trellis_fwd2_f32 stores (a store under a condition is not in the
+        // compiler's vmcnt count)
+        emu = e_use - mu_use;  // RU(b'' - mu)
+        mrow[t] = mu_use;
+      }
     }
     const float m0 = fmaxf(m0a, m0b);
     const float m1 = fmaxf(m1a, m1b);
     float m = dpp_max_mirror(hi ? m1 : m0, hi ? m0 : m1);
     m = dpp_max_xor1(m);
     m = dpp_max_xor2(m);
-    const float dn = (m + e_use) - mu_use;  // RU(RU(m + b'') - mu)
+    const float dn = m + emu;  // RU(m + RU(b'' - mu))
     __builtin_amdgcn_sched_barrier(0);
     o_load = first ? obs_y(t_obs) : obs_x(t_obs);
-    // every lane stores, as in trellis_fwd2_f32 (a store under a condition is not in the compiler's
-    // vmcnt count); the shift is one dword per sequence and step, the same in every lane
     ldst[lds_w] = dn;
-    (drow + (size_t)t * NP)[jw] = dn;
-    mrow[t] = mu_use;
-    post_max(dn, &mus[t % 3]);
+    drow += NP;  // this lane's entry of row t: one pointer per sequence, advanced in every half-step
+    *drow = dn;
+    if (post) post_max(dn, &mus[sr == 2 ? 0 : sr + 1]);
     if (first) {
       lds_barrier();
       ld8(nsrc, P);  // Y's delta_{t-1}, complete since the barrier
     }
   };
-  auto step = [&](int t) {
+  float dhX = 0.0f, dhY = 0.0f;
+  float* pX = dX + jw;  // this lane's entry of the row last stored
+  float* pY = dY + jw;
+  auto step = [&](int t, int sr, bool meas, bool post) {
     const int cur = (t - 1) & 1, nxt = t & 1;
-    half(&lds[0][cur][rg * S], &lds[1][cur][rg * S], &lds[0][nxt][0], dX, mu[0], muX, t, eXr, eYr, oY, true,
-         clampT(t + 1));
-    half(&lds[1][cur][rg * S], &lds[0][nxt][rg * S], &lds[1][nxt][0], dY, mu[1], muY, t, eYr, eXr, oX, false,
-         clampT(t + 2));
+    half(&lds[0][cur][rg * S], &lds[1][cur][rg * S], &lds[0][nxt][0], pX, mu[0], muX, t, eXr, eYr, oY, dhX, sr,
+         std::true_type{}, meas, post, clampT(t + 1));
+    half(&lds[1][cur][rg * S], &lds[0][nxt][rg * S], &lds[1][nxt][0], pY, mu[1], muY, t, eYr, eXr, oX, dhY, sr,
+         std::false_type{}, meas, post, clampT(t + 2));
   };
-  for (int t = 1; t < T; ++t) step(t);
+  // blocks of K steps: the first measures, the last posts the maximum that the next block measures.
+  // Both flags are the same in every wave (scalar branches round the few instructions they guard):
+  // a second copy of the half-step body for the steps in between takes the kernel past 112 VGPRs.
+  for (int t = 1, sr = 0; t < T; ++t) {
+    const bool post = (t & (K - 1)) == 0;
+    step(t, sr, ((t - 1) & (K - 1)) == 0, post);
+    if (post) sr = __builtin_amdgcn_readfirstlane(sr == 2 ? 0 : sr + 1);  // a scalar register
+  }
   if (bad && lane == 0 && w == 0) {
     if (bad & 1u) args.cert[seqX] = CVK_SEQ_BADOBS;
     if (bad & 2u) args.cert[seqY] = CVK_SEQ_BADOBS;
@@ -1579,10 +1618,22 @@ __global__ __launch_bounds__(64) void ru_score_f64(RuScoreArgs r) {
   }
 }
 
+// the instantiated K nearest to the tuning key t64_f32ru_mu_every (a tie goes to the smaller)
+int ru_mu_every() {
+  const int v = tuning().t64_f32ru_mu_every;
+  if (v <= 0) return Tuning{}.t64_f32ru_mu_every;
+  return v <= 2 ? 1 : v <= 6 ? 4 : 8;
+}
+
 hipError_t launch_ru_fwd2(int np, const RuFwdArgs& fa, int64_t npairs, hipStream_t stream) {
   if (npairs <= 0) return hipSuccess;
   if (np != 256) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((trellis_fwd2_f32ru<256>), dim3((unsigned)npairs), dim3(1024), 0, stream, fa);
+  const dim3 grid((unsigned)npairs), block(1024);
+  switch (ru_mu_every()) {
+    case 1: hipLaunchKernelGGL((trellis_fwd2_f32ru<256, 1>), grid, block, 0, stream, fa); break;
+    case 4: hipLaunchKernelGGL((trellis_fwd2_f32ru<256, 4>), grid, block, 0, stream, fa); break;
+    default: hipLaunchKernelGGL((trellis_fwd2_f32ru<256, 8>), grid, block, 0, stream, fa); break;
+  }
   return hipGetLastError();
 }
 

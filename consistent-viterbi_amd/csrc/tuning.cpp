@@ -26,7 +26,7 @@ const Key kKeys[] = {
     CVK_KEY(t64_rs), CVK_KEY(t64_w2), CVK_KEY(t64_wave), CVK_KEY(t64_bal),
     CVK_KEY(t64_cp_s), CVK_KEY(t64_cp_w), CVK_KEY(t64_cp_pf), CVK_KEY(t64_bt_pf),
     CVK_KEY(t64_lo_every), CVK_KEY(t64_fixed_first), CVK_KEY(t64_fixed_chunks), CVK_KEY(t64_few),
-    CVK_KEY(t64_f32ru_first),
+    CVK_KEY(t64_f32ru_first), CVK_KEY(t64_f32ru_mu_every),
     CVK_KEY(generic_s), CVK_KEY(generic_split), CVK_KEY(generic_split_k), CVK_KEY(generic_wide),
     CVK_KEY(generic_wide_min), CVK_KEY(generic_prio), CVK_KEY(wide_s), CVK_KEY(ext_wide_min),
     CVK_KEY(chain_wide), CVK_KEY(chain_wide_min), CVK_KEY(f32_onebar), CVK_KEY(bw_global),

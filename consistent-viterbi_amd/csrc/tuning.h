@@ -67,6 +67,8 @@ struct Tuning {
                                // elements (sum of lengths) of a call that takes it (0: never)
   int t64_f32ru_first = 16777216;  // certified f32 round-up first pass: the fewest elements of a call that takes it
                                // instead of the integer pass (0: never; a call below it follows t64_fixed_first)
+  int t64_f32ru_mu_every = 4;  // the round-up forward takes the row maximum at every K-th step: the nearest of
+                               // K = 1 / 4 / 8 (<= 0: the default); rows and shifts differ, results do not
   int t64_fixed_chunks = 8;    // the pass's chunks pipelined over two streams, at least min(this, nseq / 2048)
                                // (<= 64); 0: back to back on one stream, one chunk under the workspace cap
   // ---- generic and wide kernels (kernels/trellis.hip) ----

@@ -6,7 +6,7 @@ in include/cviterbi.h (libcviterbi.so: hand-written gfx950 HIP kernels).
 from ._lib import CVError, EXPORTS, LIB_PATH  # noqa: F401
 from .hmm import HMM, tuning_keys  # noqa: F401
 from .decode import (constrained_pairs, constrained_partials, constrained_select, decode, decode_batch, decode_batch_device, decode_constrained_device, decode_constrained_exchange,  # noqa: F401
-                     decode_constrained, decode_forced_components, decode_superseq_cp, device_memory, f32ru_trace, last_first_pass_kind, last_suffix_traced, last_fixed_first_stats, last_superseq_stats, last_t64_stats, last_timing, timing_begin,
+                     decode_constrained, decode_forced_components, decode_superseq_cp, device_memory, f32ru_trace, f32ru_trace_ragged, last_first_pass_kind, last_suffix_traced, last_fixed_first_stats, last_superseq_stats, last_t64_stats, last_timing, timing_begin,
                      timing_end)
 from .counts import (expected_counts, expected_counts_device, expected_counts_emissions,  # noqa: F401
                      expected_counts_emissions_device, reestimate)

@@ -51,7 +51,7 @@ EXPORTS = [
     "cv_loglik_grad_emissions", "cv_loglik_grad_emissions_device",
     "cv_sample_batch", "cv_sample_batch_device",
     "cv_last_t64_stats", "cv_last_fixed_first_stats", "cv_hmm_fit_last_stats",
-    "cv_last_first_pass_kind", "cv_f32ru_trace",
+    "cv_last_first_pass_kind", "cv_f32ru_trace", "cv_f32ru_trace_ragged",
 ]
 
 
@@ -163,6 +163,7 @@ def lib():
         "cv_last_fixed_first_stats": ([P, P, I32], I32),
         "cv_last_first_pass_kind": ([P], I32),
         "cv_f32ru_trace": ([P, I64, I64, P, P, P, P, P, P], S),
+        "cv_f32ru_trace_ragged": ([P, I64, P, P, P, P, P, P, P], S),
         "cv_device_memory": ([P, P], S),
         "cv_solver_create": ([ctypes.c_char_p, P, P, P], S),
         "cv_solver_solve": ([P], S),

@@ -321,6 +321,22 @@ def f32ru_trace(hmm: HMM, obs) -> dict:
     return dict(rows=rows.transpose(1, 0, 2), mu=mu, r=r, E=E, path=path)
 
 
+def f32ru_trace_ragged(hmm: HMM, offsets, obs) -> dict:
+    """Test hook (cv_f32ru_trace_ragged): f32ru_trace on sequences of several lengths, sequences 2k
+    and 2k + 1 of one length; rows [elements, N], mu, r and path by element, E [S]."""
+    offsets = np.ascontiguousarray(offsets, np.int64)
+    obs = np.ascontiguousarray(obs, np.int32)
+    S, ne, N = len(offsets) - 1, int(offsets[-1]), hmm.nstates()
+    assert obs.shape == (ne,)
+    rows = np.empty((ne, N), np.float32)
+    mu, r = np.empty(ne, np.float32), np.empty(ne, np.float32)
+    E, path = np.empty(S, np.float32), np.empty(ne, np.int32)
+    ptr = lambda x: x.ctypes.data_as(ctypes.c_void_p)
+    L.check(L.lib().cv_f32ru_trace_ragged(hmm.handle, S, ptr(offsets), ptr(obs), ptr(rows), ptr(mu), ptr(r), ptr(E),
+                                          ptr(path)))
+    return dict(rows=rows, mu=mu, r=r, E=E, path=path)
+
+
 def device_memory() -> dict:
     """Device bytes this process's library holds now and at most (cv_device_memory)."""
     cur, peak = ctypes.c_int64(), ctypes.c_int64()

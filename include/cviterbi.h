@@ -228,6 +228,10 @@ CV_API void cv_hmm_destroy(cv_hmm* h);
  *                         so every row is an upper bound; the f64 fold along the path certifies it);
  *                         a call below it follows t64_fixed_first.  Same counters, guard and fallback
  *                         (cv_last_first_pass_kind says which pass ran).  0: never
+ *   t64_f32ru_mu_every 4  that pass's forward shifts every row by a per-sequence prediction of the
+ *                         drift per step and takes the row maximum, which corrects it, at every K-th
+ *                         step only: the nearest of K = 1 / 4 / 8 (<= 0: the default).  The rows and
+ *                         shifts it stores differ with K; what a decode returns does not
  *   t64_fixed_chunks 8    either pass in chunks pipelined over two streams: at least
  *                         min(this, sequences / 2048) chunks (<= 64) out of a double-buffered workspace
  *                         (each chunk half the workspace cap), a chunk's certificate backtrack and score
@@ -337,6 +341,12 @@ CV_API int32_t cv_last_first_pass_kind(const cv_hmm* h);
  * (element 0 of a sequence is 0), e_last [nseq], path [nseq * T]. */
 CV_API cv_status cv_f32ru_trace(cv_hmm* h, int64_t nseq, int64_t T, const int32_t* obs, float* rows, float* mu,
                                 float* r, float* e_last, int32_t* path);
+/* Test hook too, not part of the decoding API: the same on sequences of several lengths (offsets
+ * [nseq + 1] from 0, every length at least 1; at most 2^22 elements):
+ * sequences 2k and 2k + 1 are run as a pair and must have one length.  rows [elements][N]; mu, r
+ * and path by element. */
+CV_API cv_status cv_f32ru_trace_ragged(cv_hmm* h, int64_t nseq, const int64_t* offsets, const int32_t* obs,
+                                       float* rows, float* mu, float* r, float* e_last, int32_t* path);
 /* Device timings of the last decode call on this handle (synchronizes its events). */
 CV_API cv_status cv_last_timing(cv_hmm* h, cv_timing* out);
 /* Device timings summed over EVERY decode call on this handle from cv_timing_begin to

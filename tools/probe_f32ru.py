@@ -15,11 +15,17 @@ Tables (host, f64; G = 2^-16):
   cb_o = rint(max_j fl(b[j,o] + ca_j) / G) G,   b''[j,o] = RU(b[j,o] + (ca_j - cb_o))
   pi'[j] = RU(pi[j] - ca_j)            (a column or observation of -inf alone: shift 0)
   (ca_j - cb_o is exact on the grid, so each entry is ONE real sum, rounded up exactly.)
-Rows:
+Rows (every = K, a power of two; dhat, f32 per sequence, starts at 0 and predicts the drift per step):
   v_0[j] = RU(pi'[j] + b''[j,o_0])
-  mu_t = max(max_j v_{t-1}[j], -FLT_MAX);  m = max_i RU(v_{t-1}[i] + a'[i,j]);
-  x = RU(m + b''[j,o_t]);  v_t[j] = RU(x - mu_t)
+  measured step, (t - 1) % K == 0:  m_raw = max(max_j v_{t-1}[j], -2^126);
+      for t > 1:  d = RU(dhat + (m_raw / K if |m_raw| >= 2^-64 else 0)),  dhat = d if |d| < 64 else 0
+      mu_t = RU(m_raw + dhat)
+  any other step:  mu_t = dhat
+  m = max_i RU(v_{t-1}[i] + a'[i,j]);  v_t[j] = RU(m + RU(b''[j,o_t] - mu_t))
   C_0 = cb_{o_0};  C_t = C_{t-1} + cb_{o_t} + mu_t;   v_t[j] + C_t >= D_t[j] (the real recurrence)
+  (m_raw / K is exact: a power of two, and no result in the subnormal range.  -2^126, not -FLT_MAX: b'' can
+  exceed 0 by a grid step, and RU(b'' + FLT_MAX) would be +inf.  A row of -inf alone gives m_raw = -2^126 and
+  takes dhat back to 0; later rows stay -inf without a NaN.)
 Backtrack (RU adds):
   j* = first argmax of v_{T-1}, E = the largest other entry;
   step t into cur = p_t: s_i = RU(v_{t-1}[i] + a'[i,cur]), w = first argmax, p_{t-1} = w,
@@ -32,7 +38,7 @@ Certificate (f64, beside the fold L_0 = pi[p_0] + b[p_0,o_0], L_t = (L_{t-1} + a
   Chat_t = (Chat_{t-1} + cb_{o_t}) + mu_t, then + 2^-50 (|Chat_{t-1}| + |cb_{o_t}| + |mu_t|)
   (an infinite r_t or E counts 0 in s: the comparison is then +inf > sigma, or NaN and fails).
 
-Usage: python tools/probe_f32ru.py [B] [chunk]
+Usage: python tools/probe_f32ru.py [B] [chunk] [K]
 """
 import importlib.util
 import os
@@ -46,6 +52,11 @@ GRID_MAX = 2.0 ** 30  # |shift| below this: sums and differences of two shifts a
 FLT_MAX = np.float32(3.4028234663852886e38)
 U = 2.0 ** -53
 F32 = np.float32
+SHIFT_NAME = "folded predicted shift"
+EVERY = 4  # the default K of forward(): the row maximum is taken at every K-th step
+MRAW_MIN = np.float32(-(2.0 ** 126))  # the clamp of a row maximum: b'' - mu stays finite under RU
+MRAW_TINY = np.float32(2.0 ** -64)  # a smaller row maximum adds nothing to the predictor
+DHAT_LIMIT = np.float32(64.0)  # the predictor returns to 0 at or beyond this, or when not finite
 
 
 def two_sum_err(x, y, s):
@@ -122,27 +133,50 @@ def _exact_in_f64(*arrs):
     return hi == 0.0 or hi / lo < 2.0 ** 27
 
 
-def forward(tb, obs, add=ru_add):
-    """obs [S, T]; rows [T, S, N] f32 and mu [S, T] f32 (mu[:, 0] = 0, unused)."""
+def shift_update(dhat, m_raw, every, add=ru_add):
+    """The predictor's update at a measured step t > 1: dhat + m_raw / every, 0 outside (-64, 64).
+    A row maximum below 2^-64 in magnitude counts 0, so the power-of-two scaling is exact in every
+    denormal mode."""
+    inc = np.where(np.abs(m_raw) >= MRAW_TINY, m_raw * F32(1.0 / every), F32(0)).astype(F32)
+    d = add(dhat, inc)
+    with np.errstate(invalid="ignore"):
+        return np.where(np.abs(d) < DHAT_LIMIT, d, F32(0)).astype(F32)
+
+
+def forward(tb, obs, add=ru_add, every=EVERY, state=None):
+    """obs [S, T]; rows [T, S, N] f32 and mu [S, T] f32 (mu[:, 0] = 0, unused).  every = K, a
+    power of two: the row maximum is taken at the steps t with (t - 1) % K == 0 only.  state, a
+    dict, receives dhat [S, T] (the predictor after step t)."""
+    assert every >= 1 and every & (every - 1) == 0
     a1, b2, p1 = tb["a1"], tb["b2"], tb["p1"]
     S, T = obs.shape
     N = a1.shape[0]
     rows = np.empty((T, S, N), F32)
     mu = np.zeros((S, T), F32)
+    dh = np.zeros((S, T), F32)
     v = add(p1[None, :], b2[:, obs[:, 0]].T)
     rows[0] = v
     a64 = a1.astype(np.float64)
+    dhat = np.zeros(S, F32)
     for t in range(1, T):
-        m_t = np.maximum(v.max(axis=1), -FLT_MAX)
+        if (t - 1) % every == 0:
+            m_raw = np.maximum(v.max(axis=1), MRAW_MIN)
+            if t > 1:
+                dhat = shift_update(dhat, m_raw, every, add)
+            m_t = add(m_raw, dhat)
+        else:
+            m_t = dhat
+        dh[:, t] = dhat
         if add is ru_add and _exact_in_f64(v, a1):
             # RU is monotone and the f64 sums are exact: the maximum of the sums, rounded once
             with np.errstate(invalid="ignore"):
                 m = ru32((v.astype(np.float64)[:, :, None] + a64[None, :, :]).max(axis=1))
         else:
             m = add(v[:, :, None], a1[None, :, :]).max(axis=1)
-        x = add(m, b2[:, obs[:, t]].T)
-        v = add(x, -m_t[:, None])
+        v = add(m, add(b2[:, obs[:, t]].T, -m_t[:, None]))
         rows[t], mu[:, t] = v, m_t
+    if state is not None:
+        state["dhat"] = dh
     return rows, mu
 
 
@@ -173,8 +207,9 @@ def _absfin(x):
     return np.where(np.isinf(x), 0.0, np.abs(x))
 
 
-def certify(pi, a, b, tb, obs, mu, path, r, E):
-    """cert [S] bool, score [S] f64: the fold along the path and the certificate beside it."""
+def certify(pi, a, b, tb, obs, mu, path, r, E, slack=None):
+    """cert [S] bool, score [S] f64: the fold along the path and the certificate beside it.
+    slack, a dict, receives "min": the smallest lhs - rhs of each sequence, the end included."""
     S, T = obs.shape
     ca, cb, ks = tb["ca"], tb["cb"], tb["ks"]
     mu, r, E = (np.asarray(x, np.float64) for x in (mu, r, E))
@@ -187,27 +222,33 @@ def certify(pi, a, b, tb, obs, mu, path, r, E):
         L = pi[p] + b[p, obs[:, 0]]
         C = cb[obs[:, 0]].copy()
         ok = np.ones(S, bool)
+        low = np.full(S, np.inf)
         for t in range(1, T):
             pp, p = p, path[:, t]
             lhs = L + a[pp, p]
             rhs = (r[:, t] + ca[p]) + C
+            low = np.fmin(low, lhs - rhs)
             ok &= (lhs - rhs) > sigma(t, _absfin(r[:, t]) + np.abs(ca[p]) + np.abs(C) + np.abs(lhs))
             L = lhs + b[p, obs[:, t]]
             c_t = cb[obs[:, t]]
             s = np.abs(C) + np.abs(c_t) + np.abs(mu[:, t])
             C = ((C + c_t) + mu[:, t]) + 2.0 ** -50 * s
         ok &= (L - (E + C)) > sigma(T, _absfin(E) + np.abs(C) + np.abs(L))
+        low = np.fmin(low, L - (E + C))
+    if slack is not None:
+        slack["min"] = low
     return ok, L
 
 
-def decode(pi, a, b, obs):
+def decode(pi, a, b, obs, every=EVERY):
     """The whole first pass for sequences of one length: path [S, T], cert [S], score [S], parts."""
     tb = tables(pi, a, b)
-    rows, mu = forward(tb, obs)
+    state, slack = {}, {}
+    rows, mu = forward(tb, obs, every=every, state=state)
     path, r, E = backtrack(tb, rows)
     cert, score = certify(np.asarray(pi, np.float64), np.asarray(a, np.float64), np.asarray(b, np.float64), tb, obs,
-                          mu, path, r, E)
-    return path, cert, score, dict(rows=rows, mu=mu, r=r, E=E, tb=tb)
+                          mu, path, r, E, slack=slack)
+    return path, cert, score, dict(rows=rows, mu=mu, r=r, E=E, tb=tb, dhat=state["dhat"], slack=slack["min"])
 
 
 def _load_fixed_model():
@@ -225,16 +266,18 @@ def main():
     FX = _load_fixed_model()
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 512
     chunk = int(sys.argv[2]) if len(sys.argv) > 2 else 32
+    every = int(sys.argv[3]) if len(sys.argv) > 3 else EVERY
     c = synth.config("c4", B)
     pi, a, b = c["pi"], c["a"], c["b"]
     T = 512
     obs = c["obs"].reshape(B, T).astype(np.int64)
-    certs, certs_i, same, gaps, excess = [], [], [], [], []
+    certs, certs_i, same, gaps, loose, tops = [], [], [], [], [], []
     t0 = time.time()
     for s0 in range(0, B, chunk):
         o = obs[s0:s0 + chunk]
         p64, g64 = FX.decode64(pi, a, b, o)
-        pr, cert, _, _ = decode(pi, a, b, o)
+        pr, cert, _, parts = decode(pi, a, b, o, every)
+        loose.append(g64 - parts["slack"]); tops.append(np.abs(parts["rows"].max(axis=2)).max())
         _, cert_i, _ = FX.decode(pi, a, b, o)
         eq = (pr == p64).all(axis=1)
         assert np.all(eq[cert]), "a certified round-up path differs from the f64 path"
@@ -243,13 +286,16 @@ def main():
               f" (integer model {np.concatenate(certs_i).mean():.4f}), path == f64 {np.concatenate(same).mean():.4f}",
               flush=True)
     cert = np.concatenate(certs); cert_i = np.concatenate(certs_i); eq = np.concatenate(same); g = np.concatenate(gaps)
-    print(f"\nB={B} N=256 T=512 (config 4, first {B} sequences), f32 round-up first pass")
+    print(f"\nB={B} N=256 T=512 (config 4, first {B} sequences), f32 round-up first pass, {SHIFT_NAME}, K = {every}")
     print(f"f64 path margin quantiles 1/5/10/50% = {np.quantile(g, [0.01, 0.05, 0.10, 0.5])}")
     print(f"round-up path == f64 path {eq.mean():.4f}; CERTIFIED {cert.mean():.4f} ({cert.sum()} of {B});"
           f" integer model {cert_i.mean():.4f} ({cert_i.sum()} of {B})")
     print(f"certified paths equal to the f64 path: {int((eq & cert).sum())} of {int(cert.sum())}")
     print(f"projected fallback of 65,536: {(1 - cert.mean()) * 65536:.0f} sequences")
     print(f"uncertified margins (f64): {np.sort(g[~cert])}")
+    lo = np.concatenate(loose)
+    print(f"looseness (f64 margin - smallest lhs - rhs) median/90%/max = {np.quantile(lo, [0.5, 0.9, 1.0])};"
+          f" largest abs(row max) {max(tops):.3f}")
 
 
 if __name__ == "__main__":
