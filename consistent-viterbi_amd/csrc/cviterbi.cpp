@@ -39,6 +39,7 @@
 #include "kernels/fit.h"
 #include "kernels/emis.h"
 #include "kernels/kbest.h"
+#include "kernels/bcount.h"
 #include "kernels/posterior.h"
 #include "kernels/sample.h"
 #include "kernels/trellis.h"
@@ -298,6 +299,7 @@ struct cv_hmm {
   // cv_expected_counts*: the GEMM's partial tiles, the call's NP x NP accumulator, gamma_0 of every
   // sequence, and the host API's staging of pi_cnt [N] and a_cnt [N][N]
   DevBuf ps_xi_part, ps_xi_s, ps_g0, st_cnt;
+  DevBuf ps_bc_acc, ps_bc_sort, ps_bc_part;  // cv_expected_counts_model*: [V][NP] accumulator, sort scratch, run sums
   PinnedHost sm_pin;  // cv_sample_batch: the log-likelihoods and score planes on their way to the caller
   OrderStage ps_pin;
   // K-best workspace: the u16 back-pointers of one chunk, each sequence's last lists, the
@@ -1493,6 +1495,10 @@ struct CountsReq {
   const double* weight = nullptr;  // device, [nseq]; null: all 1
   double* egrad = nullptr;         // device, nullable, row e at egrad + e * ld_grad
   int64_t ld_grad = 0;
+  // cv_expected_counts_model*: the expected emission counts of the discrete model (bcount.hip), with
+  // grad set -- the rows w_s gamma the gradient arm stores are what the scatter by observation adds.
+  // egrad (ld_grad = N) is then the caller's gamma; null: a chunk-local workspace takes the rows
+  double* b_cnt = nullptr;  // device, nullable, [N][V]
 };
 
 // Core of cv_posterior_batch*: all pointers are device pointers except offsets_host.  Chunks of
@@ -1511,6 +1517,11 @@ struct CountsReq {
 // fold into ps_xi_s (zeroed here), and the last chunk is followed by the kernels that write
 // pi_cnt and a_cnt -- all inside the chunk's backward events, so bt_ms covers them.  With cnt->grad
 // (cv_loglik_grad_emissions*) the backward pass is the gradient arm's; nothing else differs.
+// cnt->b_cnt (cv_expected_counts_model*; with cnt->grad, the handle's own b): the rows w_s gamma of
+// the gradient arm go to cnt->egrad (the caller's gamma, stride N) or, when that is null, to a
+// chunk-local workspace (8 NP bytes per element more, under the cap); after each chunk's count GEMM
+// the rows are added by observation into ps_bc_acc (zeroed here; bcount.hip: keys, stable sort,
+// run sums, fold), and the last chunk is followed by the kernel that writes b_cnt.
 cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, const int64_t* offsets_dev,
                            const int32_t* obs_dev, const cv_opts& o, double* loglik_dev, int32_t* path_dev,
                            double* gamma_dev, uint8_t* status_dev, hipStream_t stream, const EmisSrc* emis = nullptr,
@@ -1530,14 +1541,21 @@ cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
   if (nseq == 0 && cnt) {  // overwritten, not accumulated: an empty batch counts nothing
     HIP_TRY(hipMemsetAsync(cnt->pi_cnt, 0, (size_t)h->N * 8, stream));
     HIP_TRY(hipMemsetAsync(cnt->a_cnt, 0, (size_t)h->N * h->N * 8, stream));
+    if (cnt->b_cnt) HIP_TRY(hipMemsetAsync(cnt->b_cnt, 0, (size_t)h->N * (size_t)h->V * 8, stream));
   }
   if (nseq == 0) return CV_OK;
   if (h->ws_rec) HIP_TRY(hipStreamWaitEvent(stream, h->ws_done, 0));
 
   const bool store = path_dev || gamma_dev || smp || cnt;
+  const bool bc = cnt && cnt->b_cnt;
+  if (bc && (emis || !cnt->grad || !obs_dev || gamma_dev || (cnt->egrad && cnt->ld_grad != h->N)))
+    return set_err(CV_EINTERNAL, "emission counts: the discrete model under the gradient arm only");
+  if (bc && h->V > INT32_MAX) return set_err(CV_ELIMIT, "emission counts cover V <= %d (V=%lld)", INT32_MAX, (long long)h->V);
+  const bool bc_ws = bc && !cnt->egrad;  // the rows w_s gamma go to the workspace
   const uint64_t row_bytes = (uint64_t)np * 8;
   // counts: the U row and inv of every element beside its forward row
-  const uint64_t per_elem = (store ? row_bytes : 0) + (cnt ? row_bytes + 8 : 0) + (emis ? row_bytes + 4 : 0);
+  const uint64_t per_elem =
+      (store ? row_bytes : 0) + (cnt ? row_bytes + 8 : 0) + (emis ? row_bytes + 4 : 0) + (bc_ws ? row_bytes : 0);
   // ... and the GEMM's partial tiles, under the same cap: at most cvp::kXiPartCap, and half of a
   // cap that is smaller than twice that
   uint64_t part_cap = 0;
@@ -1568,8 +1586,9 @@ cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
     if ((st = h->ps_rows.ensure((size_t)(max_elems * per_elem))) != CV_OK) return st;
   }
   // the workspace: [max_elems][NP] forward rows (store), [max_elems][NP] U rows (counts),
-  // [max_elems][NP] staged emission rows (emis), [max_elems] inv (counts), [max_elems] int32
-  // observation indices (emis); NP * 8 is a multiple of 512
+  // [max_elems][NP] staged emission rows (emis), [max_elems][NP] rows w_s gamma (emission counts
+  // without the caller's gamma), [max_elems] inv (counts), [max_elems] int32 observation indices
+  // (emis); NP * 8 is a multiple of 512
   double* ws_next = h->ps_rows.as<double>();
   auto take_rows = [&](bool on, uint64_t width) {
     double* const p = on ? ws_next : nullptr;
@@ -1579,6 +1598,7 @@ cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
   double* const ws_rows = take_rows(store, (uint64_t)np);
   double* const ws_urows = take_rows(cnt != nullptr, (uint64_t)np);
   double* const ws_emis = take_rows(emis != nullptr, (uint64_t)np);
+  double* const ws_g = take_rows(bc_ws, (uint64_t)np);
   double* const ws_inv = take_rows(cnt != nullptr, 1);
   int32_t* const ws_idx = emis ? reinterpret_cast<int32_t*>(ws_next) : nullptr;
   const int64_t xi_key = cvk::tuning().xi_part_rows;
@@ -1593,6 +1613,44 @@ cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
     if ((st = h->ps_xi_s.ensure((size_t)np * row_bytes)) != CV_OK) return st;
     if ((st = h->ps_g0.ensure((size_t)nseq * row_bytes)) != CV_OK) return st;
     HIP_TRY(hipMemsetAsync(h->ps_xi_s.p, 0, (size_t)np * row_bytes, stream));
+  }
+  // emission counts: the sort's scratch and the run sums of the largest chunk, the accumulator
+  const int64_t bc_key = cvk::tuning().bcnt_part_rows;
+  cvb::BcntArgs bq{};
+  if (bc) {
+    if (max_elems > INT32_MAX) return set_err(CV_ELIMIT, "emission counts: a chunk of %llu elements", (unsigned long long)max_elems);
+    int64_t most_runs = 1;
+    for (const auto& c : chunks) {
+      const int64_t rows = offsets_host[c.second] - offsets_host[c.first];
+      most_runs = std::max(most_runs, cvb::bcnt_max_runs(rows, cvb::bcnt_part_rows(rows, np, bc_key), h->V));
+    }
+    size_t tmp = 0;
+    hipError_t qe = cvb::bcnt_sort_tmp_bytes((int64_t)max_elems, h->V, &tmp);
+    if (qe != hipSuccess) return set_err(CV_EDEVICE, "emission-count sort sizing failed: %s", hipGetErrorString(qe));
+    auto up = [](size_t n) { return (n + 255) / 256 * 256; };
+    const size_t plane = up((size_t)max_elems * 4), tmp_b = up(tmp), keys_b = up((size_t)most_runs * 4);
+    if ((st = h->ps_bc_sort.ensure(5 * plane + tmp_b + keys_b)) != CV_OK) return st;
+    if ((st = h->ps_bc_part.ensure((size_t)most_runs * row_bytes)) != CV_OK) return st;
+    if ((st = h->ps_bc_acc.ensure((size_t)h->V * row_bytes)) != CV_OK) return st;
+    HIP_TRY(hipMemsetAsync(h->ps_bc_acc.p, 0, (size_t)h->V * row_bytes, stream));
+    char* const sp = h->ps_bc_sort.as<char>();
+    bq.key_in = reinterpret_cast<uint32_t*>(sp);
+    bq.key_out = reinterpret_cast<uint32_t*>(sp + plane);
+    bq.row_in = reinterpret_cast<int32_t*>(sp + 2 * plane);
+    bq.row_out = reinterpret_cast<int32_t*>(sp + 3 * plane);
+    bq.run = reinterpret_cast<int32_t*>(sp + 4 * plane);
+    bq.sort_tmp = sp + 5 * plane;
+    bq.sort_tmp_bytes = tmp_b;
+    bq.run_key = reinterpret_cast<uint32_t*>(sp + 5 * plane + tmp_b);
+    bq.max_runs = most_runs;
+    bq.part = h->ps_bc_part.as<double>();
+    bq.acc = h->ps_bc_acc.as<double>();
+    bq.offsets = offsets_dev;
+    bq.obs = obs_dev;
+    bq.status = status_dev;
+    bq.nobs = h->V;
+    bq.nstates = h->N;
+    bq.np = np;
   }
   if (emis) {
     if ((st = h->ps_kshift.ensure((size_t)nseq * 8)) != CV_OK) return st;
@@ -1641,6 +1699,10 @@ cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
       g.weight = cnt->weight;
       g.egrad = cnt->egrad;
       g.ld_grad = cnt->ld_grad;
+      if (bc_ws) {  // the kernels index egrad by absolute element: (ws_g - e0 NP)[e NP] = ws_g[(e - e0) NP]
+        g.egrad = reinterpret_cast<double*>(reinterpret_cast<uintptr_t>(ws_g) - (uintptr_t)g.elem_base * row_bytes);
+        g.ld_grad = np;
+      }
     }
     hipEvent_t f0 = h->ev[eb + 4 * ci], f1 = h->ev[eb + 4 * ci + 1], b0 = h->ev[eb + 4 * ci + 2], b1 = h->ev[eb + 4 * ci + 3];
     HIP_TRY(hipEventRecord(f0, stream));
@@ -1738,6 +1800,19 @@ cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
         f.a_cnt = cnt->a_cnt;
         f.pi_cnt = cnt->pi_cnt;
         err = cvp::launch_post_counts_final(f, stream);
+      }
+      if (err == hipSuccess && bc) {
+        cvb::BcntArgs b = bq;
+        b.seq_begin = c.first;
+        b.seq_end = c.second;
+        b.elem_base = g.elem_base;
+        b.nrows = x.nrows;
+        b.ld = g.ld_grad;
+        b.g = bc_ws ? ws_g : cnt->egrad + (size_t)g.elem_base * (size_t)h->N;
+        b.part_rows = cvb::bcnt_part_rows(b.nrows, np, bc_key);
+        err = cvb::launch_bcnt_chunk(b, stream);
+        if (err == hipSuccess && ci + 1 == chunks.size())
+          err = cvb::launch_bcnt_final(bq.acc, h->V, h->N, np, cnt->b_cnt, stream);
       }
       if (err != hipSuccess) return set_err(CV_EDEVICE, "expected-counts launch failed: %s", hipGetErrorString(err));
     }
@@ -2053,7 +2128,7 @@ CV_API cv_status cv_hmm_release_workspaces(cv_hmm* h) {
                     &h->chainb.rpsi, &h->chainb.rows, &h->chainb.small, &h->chainb.rpath, &h->chainb.soff,
                     &h->chainb.sobs, &h->chainb.spath, &h->chainb.sres, &h->chainb.sinit, &h->chainb.slast,
                     &h->chainb.spsi, &h->ps_rows,
-                    &h->ps_order, &h->ps_kshift, &h->st_gamma, &h->ps_xi_part, &h->ps_xi_s, &h->ps_g0, &h->st_cnt, &h->kb_bp, &h->kb_last, &h->kb_order, &h->kb_end, &h->st_count,
+                    &h->ps_order, &h->ps_kshift, &h->st_gamma, &h->ps_xi_part, &h->ps_xi_s, &h->ps_g0, &h->st_cnt, &h->ps_bc_acc, &h->ps_bc_sort, &h->ps_bc_part, &h->kb_bp, &h->kb_last, &h->kb_order, &h->kb_end, &h->st_count,
                     &h->st_emis, &h->fx_cert, &h->fx_idx, &h->fx_obs2, &h->fx_path2, &h->fx_score2, &h->fx_status2,
                     &h->ru_mu, &h->ru_r, &h->ru_e})
     b->release();
@@ -3078,6 +3153,84 @@ CV_API cv_status cv_loglik_grad_emissions(cv_hmm* h, int64_t nseq, const int64_t
   hb.fetch_seqs(status_out, h->st_status);
   if (hb.err == hipSuccess) hb.err = hipMemcpyAsync(pi_grad_out, cnt.pi_cnt, N * 8, hipMemcpyDeviceToHost, hb.stream);
   if (hb.err == hipSuccess) hb.err = hipMemcpyAsync(a_grad_out, cnt.a_cnt, N * N * 8, hipMemcpyDeviceToHost, hb.stream);
+  if ((st = hb.finish()) != CV_OK) return st;
+  for (int64_t s = 0; s < nseq; ++s)
+    if (status_out[s] == CV_SEQ_INFEASIBLE)
+      return set_err(CV_EINFEASIBLE, "sequence %lld has likelihood 0", (long long)s);
+  return CV_OK;
+}
+
+// ---- expected counts of the whole discrete model: cv_expected_counts_model* --------------------
+// cv_expected_counts* with per-sequence weights (null: all 1) and the emission counts b_cnt [N][V]:
+// the gradient arm on the handle's own b, its rows w_s gamma scattered by observation (bcount.hip).
+CV_API cv_status cv_expected_counts_model_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
+                                                 const int64_t* offsets_dev, const int32_t* obs_dev,
+                                                 const double* weight_dev, const cv_opts* opts, double* loglik_dev,
+                                                 double* pi_cnt_dev, double* a_cnt_dev, double* b_cnt_dev,
+                                                 double* gamma_dev, uint8_t* status_dev) {
+  if (!h) return set_err(CV_EINVAL, "null handle");
+  if (nseq < 0) return set_err(CV_EINVAL, "nseq < 0");
+  if (!pi_cnt_dev || !a_cnt_dev || !b_cnt_dev) return set_err(CV_EINVAL, "null device buffer");
+  if (nseq > 0 && (!offsets_dev || !obs_dev || !loglik_dev || !status_dev)) return set_err(CV_EINVAL, "null device buffer");
+  const cv_opts o = opts ? *opts : default_opts();
+  cv_status st = posterior_opts_ok(h, o);
+  if (st != CV_OK) return st;
+  CV_LOCK(h);
+  if ((st = set_device(h)) != CV_OK) return st;
+  hipStream_t stream = o.stream ? (hipStream_t)o.stream : h->stream;
+  CountsReq cnt{pi_cnt_dev, a_cnt_dev};
+  cnt.grad = true;
+  cnt.weight = weight_dev;
+  cnt.egrad = gamma_dev;
+  cnt.ld_grad = h->N;
+  cnt.b_cnt = b_cnt_dev;
+  return posterior_device(h, nseq, offsets_host, offsets_dev, obs_dev, o, loglik_dev, nullptr, nullptr, status_dev, stream,
+                          nullptr, nullptr, &cnt);
+}
+
+// Host arrays: pi_cnt, a_cnt, b_cnt and the weights ride in st_cnt, gamma in st_gamma.
+CV_API cv_status cv_expected_counts_model(cv_hmm* h, int64_t nseq, const int64_t* offsets, const int32_t* obs,
+                                          const double* weight, const cv_opts* opts, double* loglik_out,
+                                          double* pi_cnt_out, double* a_cnt_out, double* b_cnt_out, double* gamma_out,
+                                          uint8_t* status_out) {
+  if (!h) return set_err(CV_EINVAL, "null handle");
+  if (nseq < 0 || !pi_cnt_out || !a_cnt_out || !b_cnt_out) return set_err(CV_EINVAL, "null argument");
+  if (nseq > 0 && (!offsets || !obs || !loglik_out || !status_out)) return set_err(CV_EINVAL, "null argument");
+  cv_opts o = opts ? *opts : default_opts();
+  cv_status st = posterior_opts_ok(h, o);
+  if (st != CV_OK) return st;
+  CV_LOCK(h);
+  if ((st = set_device(h)) != CV_OK) return st;
+  const size_t N = (size_t)h->N, V = (size_t)h->V;
+  if (nseq == 0) {  // overwritten, not accumulated
+    std::fill(pi_cnt_out, pi_cnt_out + N, 0.0);
+    std::fill(a_cnt_out, a_cnt_out + N * N, 0.0);
+    std::fill(b_cnt_out, b_cnt_out + N * V, 0.0);
+    return CV_OK;
+  }
+  HostBatch hb{h, nseq, offsets, obs, o.stream ? (hipStream_t)o.stream : h->stream};
+  if ((st = hb.stage(o, 0, 1)) != CV_OK) return st;
+  if (gamma_out && (st = h->st_gamma.ensure(hb.plane() * N * 8)) != CV_OK) return st;
+  if ((st = h->st_cnt.ensure((N + N * N + N * V + (weight ? (size_t)nseq : 0)) * 8)) != CV_OK) return st;
+  CountsReq cnt{h->st_cnt.as<double>(), h->st_cnt.as<double>() + N};
+  cnt.grad = true;
+  cnt.b_cnt = h->st_cnt.as<double>() + N + N * N;
+  if (weight) {
+    double* const wd = cnt.b_cnt + N * V;
+    HIP_TRY(hipMemcpyAsync(wd, weight, (size_t)nseq * 8, hipMemcpyHostToDevice, hb.stream));
+    cnt.weight = wd;
+  }
+  cnt.egrad = gamma_out ? h->st_gamma.as<double>() : nullptr;
+  cnt.ld_grad = (int64_t)N;
+  st = posterior_device(h, nseq, offsets, h->st_off.as<int64_t>(), h->st_obs.as<int32_t>(), o, h->st_score.as<double>(),
+                        nullptr, nullptr, h->st_status.as<uint8_t>(), hb.stream, nullptr, nullptr, &cnt);
+  if (st != CV_OK) return hb.fail(st);
+  if (gamma_out) hb.fetch_elems(gamma_out, h->st_gamma, N);
+  hb.fetch_seqs(loglik_out, h->st_score);
+  hb.fetch_seqs(status_out, h->st_status);
+  if (hb.err == hipSuccess) hb.err = hipMemcpyAsync(pi_cnt_out, cnt.pi_cnt, N * 8, hipMemcpyDeviceToHost, hb.stream);
+  if (hb.err == hipSuccess) hb.err = hipMemcpyAsync(a_cnt_out, cnt.a_cnt, N * N * 8, hipMemcpyDeviceToHost, hb.stream);
+  if (hb.err == hipSuccess) hb.err = hipMemcpyAsync(b_cnt_out, cnt.b_cnt, N * V * 8, hipMemcpyDeviceToHost, hb.stream);
   if ((st = hb.finish()) != CV_OK) return st;
   for (int64_t s = 0; s < nseq; ++s)
     if (status_out[s] == CV_SEQ_INFEASIBLE)

@@ -94,6 +94,11 @@ struct Tuning {
   // ---- expected counts (kernels/counts.hip) ----
   int xi_part_rows = 0;        // > 0: rows per part of post_xi_gemm, rounded up to a multiple of 4 (0: by
                                // rule, cvp::post_xi_part_rows); a test hook: several parts from a small input
+  // ---- expected emission counts (kernels/bcount.hip) ----
+  int bcnt_part_rows = 0;      // > 0: sorted rows per part of bcnt_gather (0: by rule, cvb::bcnt_part_rows); a
+                               // test hook: segments over many parts from a small input.  Not bit-identical
+                               // either: it moves the boundaries of the runs, so the same terms are added in
+                               // another grouping; b_cnt holds its bound under every value
 };
 
 // the current call's tuning: the handle's snapshot inside a host API call, else the defaults

@@ -9,7 +9,8 @@ from .decode import (constrained_pairs, constrained_partials, constrained_select
                      decode_constrained, decode_forced_components, decode_superseq_cp, device_memory, f32ru_trace, f32ru_trace_ragged, last_first_pass_kind, last_suffix_traced, last_fixed_first_stats, last_superseq_stats, last_t64_stats, last_timing, timing_begin,
                      timing_end)
 from .counts import (expected_counts, expected_counts_device, expected_counts_emissions,  # noqa: F401
-                     expected_counts_emissions_device, reestimate)
+                     expected_counts_emissions_device, expected_counts_model, expected_counts_model_device,
+                     reestimate, reestimate_model)
 from .emissions import decode_emissions, decode_emissions_device  # noqa: F401
 from .grad import loglik_grad_emissions, loglik_grad_emissions_device  # noqa: F401
 from . import autograd  # noqa: F401

@@ -1,4 +1,6 @@
-"""torch.autograd for the sequence log-likelihood under emission scores (cv_loglik_grad_emissions*).
+"""torch.autograd for the sequence log-likelihood: under emission scores (sequence_loglik,
+cv_loglik_grad_emissions*) and of the discrete model with a learnable emission table
+(discrete_loglik, cv_expected_counts_model*).
 
     loglik = cviterbi.autograd.sequence_loglik(emis, offsets, log_pi, log_a)   # [B], log10
     (-loglik.sum()).backward()          # gradients in emis, log_pi and log_a
@@ -14,16 +16,25 @@ scores s and parameters (lp, la) use
 
 whose gradients are then the natural-log ones (the two factors cancel).  Differentiable once
 (no double backward); f64 only.
+
+    loglik = cviterbi.autograd.discrete_loglik(obs, offsets, log_pi, log_a, log_b)   # [B], log10
+    (-loglik.sum()).backward()          # gradients in log_pi, log_a and log_b
+
+is the same for the discrete model: obs int32 [L] on the GPU, log_b [N, V]; the forward pass is the
+scoring mode of posterior_batch_device, the backward pass one expected_counts_model_device call.
 """
 from __future__ import annotations
 
 import numpy as np
 
+from .counts import expected_counts_model_device
 from .emissions import _dev_ld, posterior_emissions_device
 from .grad import loglik_grad_emissions_device
 from .hmm import HMM
+from .posterior import posterior_batch_device
 
 _FN = None
+_DFN = None
 _SIDE = {}  # device index -> the stream that stands in for torch's legacy default stream
 
 
@@ -162,4 +173,123 @@ def sequence_loglik(emis, offsets, log_pi, log_a, *, forced=None, hmm=None, kern
     call = dict(hmm=hmm, offsets_host=off, offsets_dev=torch.from_numpy(off).to(emis.device), forced_dev=forced_dev,
                 kernel=kernel, workspace_bytes=workspace_bytes)
     loglik, status = _function().apply(emis, log_pi, log_a, call)
+    return (loglik, status) if return_status else loglik
+
+
+def _discrete_function():
+    """The torch.autograd.Function of discrete_loglik, built at first use."""
+    global _DFN
+    if _DFN is not None:
+        return _DFN
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class DiscreteLoglik(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, log_pi, log_a, log_b, call):
+            ctx.call = call
+            ctx.param_devices = (log_pi.device, log_a.device, log_b.device)
+            obs = call["obs"]
+            nseq = len(call["offsets_host"]) - 1
+            loglik = torch.empty(nseq, dtype=torch.float64, device=obs.device)
+            status = torch.empty(nseq, dtype=torch.uint8, device=obs.device)
+            _ordered(torch, obs.device, lambda stream: posterior_batch_device(
+                call["hmm"], call["offsets_dev"], obs, loglik, status, offsets_host=call["offsets_host"],
+                forced_dev=call["forced_dev"], kernel=call["kernel"], stream=stream,
+                workspace_bytes=call["workspace_bytes"]))
+            ctx.mark_non_differentiable(status)
+            return loglik, status
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_loglik, _grad_status):
+            call = ctx.call
+            hmm, obs = call["hmm"], call["obs"]
+            n, v, dev = hmm.nstates(), hmm.nobs(), obs.device
+            off = call["offsets_host"]
+            nseq = len(off) - 1
+            weight = grad_loglik.to(device=dev, dtype=torch.float64).contiguous()
+            loglik = torch.empty(nseq, dtype=torch.float64, device=dev)
+            status = torch.empty(nseq, dtype=torch.uint8, device=dev)
+            pi_grad = torch.empty(n, dtype=torch.float64, device=dev)
+            a_grad = torch.empty((n, n), dtype=torch.float64, device=dev)
+            b_grad = torch.empty((n, v), dtype=torch.float64, device=dev)
+            _ordered(torch, dev, lambda stream: expected_counts_model_device(
+                hmm, call["offsets_dev"], obs, loglik, pi_grad, a_grad, b_grad, status, weight_dev=weight,
+                offsets_host=off, forced_dev=call["forced_dev"], kernel=call["kernel"], stream=stream,
+                workspace_bytes=call["workspace_bytes"]))
+            grads = (pi_grad, a_grad, b_grad)
+            return tuple(g.to(d) if need else None
+                         for g, d, need in zip(grads, ctx.param_devices, ctx.needs_input_grad[:3])) + (None,)
+
+    _DFN = DiscreteLoglik
+    return _DFN
+
+
+def _check_discrete(obs, log_pi, log_a, log_b):
+    import torch
+
+    for name, x in (("obs", obs), ("log_pi", log_pi), ("log_a", log_a), ("log_b", log_b)):
+        if not isinstance(x, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor, got {type(x).__name__}")
+    if obs.dtype != torch.int32:
+        raise ValueError(f"obs must be int32, got {obs.dtype}")
+    for name, x in (("log_pi", log_pi), ("log_a", log_a), ("log_b", log_b)):
+        if x.dtype != torch.float64:
+            raise ValueError(f"{name} must be float64, got {x.dtype}")
+    if log_pi.dim() != 1 or log_pi.shape[0] < 1 or tuple(log_a.shape) != (log_pi.shape[0], log_pi.shape[0]):
+        raise ValueError(f"log_pi {tuple(log_pi.shape)} and log_a {tuple(log_a.shape)} must be [N] and [N, N]")
+    if log_b.dim() != 2 or log_b.shape[0] != log_pi.shape[0] or log_b.shape[1] < 1:
+        raise ValueError(f"log_b must be [N = {log_pi.shape[0]}, V >= 1], got {tuple(log_b.shape)}")
+    if obs.device.type != "cuda":
+        raise ValueError(f"obs must be on a GPU, it is on {obs.device}")
+    for name, x in (("log_pi", log_pi), ("log_a", log_a), ("log_b", log_b)):
+        if x.device.type != "cpu" and x.device != obs.device:
+            raise ValueError(f"{name} is on {x.device}, obs on {obs.device}")
+    if obs.dim() != 1 or not obs.is_contiguous():
+        raise ValueError(f"obs must be a contiguous [sum T] vector, got {tuple(obs.shape)}")
+    return torch
+
+
+def discrete_loglik(obs, offsets, log_pi, log_a, log_b, *, forced=None, hmm=None, kernel="auto", workspace_bytes=0,
+                    return_status=False):
+    """log10 P(o_s | pi, A, b) of the CSR sequences `offsets` ([B + 1], host integers or a torch
+    tensor) over the observation indices obs -> loglik f64[B] on obs's device, differentiable in
+    log_pi, log_a and log_b.
+
+    obs: int32 [L] on a GPU, contiguous, values in [0, V) (a sequence with a value outside is
+    SEQ_BADOBS); log_pi [N], log_a [N, N] and log_b [N, V]: f64 torch tensors, log10 (-inf =
+    impossible), on the CPU or on obs's device.  forced (optional, int32 [L]): -1 free, s >= 0
+    admits only state s.  Wrong dtypes, devices or shapes raise ValueError before anything is
+    launched.
+
+    hmm=None builds a handle from the current values of the three parameters at each call; a
+    caller who rebuilds the handle once per optimiser step passes hmm= and so vouches that it
+    holds these values on obs's device; the gradients are still returned.
+
+    The gradient of a loss through loglik is one expected_counts_model_device call with
+    grad_output as the weights: returned for log_pi, log_a and log_b only where they require grad;
+    exactly 0 on every -inf parameter, and in log_b for every value no OK sequence observes.
+    Sequences that are not SEQ_OK get the loglik that score_batch gives them and a zero gradient,
+    whatever grad_output holds for them; return_status=True also returns their statuses."""
+    torch = _check_discrete(obs, log_pi, log_a, log_b)
+    n, v = log_b.shape
+    if torch.is_tensor(offsets):
+        offsets = offsets.detach().cpu().numpy()
+    off = np.array(offsets, np.int64)  # a copy: the call keeps it until backward
+    if off.ndim != 1 or off.shape[0] < 1 or np.any(np.diff(off) < 0) or off[0] < 0 or off[-1] > obs.shape[0]:
+        raise ValueError(f"offsets must be non-decreasing [B + 1] within obs's {obs.shape[0]} elements")
+    forced_dev = None
+    if forced is not None:
+        forced_dev = torch.as_tensor(forced).to(device=obs.device, dtype=torch.int32).contiguous()
+        if forced_dev.dim() != 1 or forced_dev.shape[0] < int(off[-1]):
+            raise ValueError(f"forced must be [sum T], got {tuple(forced_dev.shape)}")
+    if hmm is None:
+        hmm = HMM(log_pi.detach().cpu().numpy(), log_a.detach().cpu().numpy(), log_b.detach().cpu().numpy(),
+                  device=obs.device.index or 0)
+    elif hmm.nstates() != n or hmm.nobs() != v:
+        raise ValueError(f"hmm has {hmm.nstates()} states and {hmm.nobs()} observation values, log_b [{n}, {v}]")
+    call = dict(hmm=hmm, obs=obs, offsets_host=off, offsets_dev=torch.from_numpy(off).to(obs.device),
+                forced_dev=forced_dev, kernel=kernel, workspace_bytes=workspace_bytes)
+    loglik, status = _discrete_function().apply(log_pi, log_a, log_b, call)
     return (loglik, status) if return_status else loglik

@@ -257,6 +257,10 @@ CV_API void cv_hmm_destroy(cv_hmm* h);
  *                         multiple of 4 (0: by rule, from the chunk's rows and NP); a test hook: several
  *                         parts from a small input.  Not bit-identical: it regroups the sums of
  *                         non-negative terms; the counts hold their bound under every value
+ *   bcnt_part_rows 0      cv_expected_counts_model*: > 0 the sorted rows per part of the emission-count
+ *                         gather (0: by rule, from the chunk's rows and NP); a test hook: segments over many
+ *                         parts from a small input.  Not bit-identical: it regroups the sums; b_cnt holds
+ *                         its bound under every value
  * The bw_* keys are not bit-identical: the E-step sums are f64 atomic adds in arrival order, so
  * they hold to the fitting tolerance (1e-9 on the log10 parameters) instead.
  * Unknown keys and values outside int32 are CV_EINVAL.  cv_tuning_key(i) lists the keys
@@ -822,6 +826,73 @@ CV_API cv_status cv_loglik_grad_emissions_device(cv_hmm* h, int64_t nseq, const 
                                                  const double* weight_dev, const cv_opts* opts, double* loglik_dev,
                                                  double* pi_grad_dev, double* a_grad_dev, double* emis_grad_dev,
                                                  int64_t ld_grad, uint8_t* status_dev);
+
+/* ---- expected counts of the whole discrete model (full EM; the gradient in log10 b) ------------
+ * cv_expected_counts with a weight per sequence and the statistics of the emission table b, for
+ * the model the handle holds (read exactly as cv_posterior_batch reads it).  Over the sequences s
+ * with status CV_SEQ_OK, gamma_e the posterior state marginal of element e:
+ *   b_cnt_out[j * V + v] = sum_s w_s sum_{e in s, obs[e] = v} gamma_e[j]      (b's own layout:
+ *                          state-major, V = the product of bdims, v the flattened index of
+ *                          cv_obs_flatten),
+ *   pi_cnt_out[i]        = sum_s w_s gamma_0(s)[i],
+ *   a_cnt_out[i * N + j] = sum_s w_s sum_t xi_t(s)(i, j).
+ * weight null means all 1: the three arrays are then the expected counts of an E-step, and
+ * loglik_out, pi_cnt_out, a_cnt_out, gamma_out and status_out are what cv_expected_counts returns
+ * for the same arguments, bit for bit (weight all 1.0 likewise: the weight enters as one product
+ * after the division).  With weights the arrays are the gradient of F = sum_s w_s log10 P(o_s) in
+ * log10 b, log10 pi and log10 A, in log10 units on both sides, with the weight semantics of
+ * cv_loglik_grad_emissions: gamma_out (nullable) holds the rows w_s gamma_e, zeros for a sequence
+ * that is not OK; such a sequence contributes nothing WHATEVER its weight holds (a select on the
+ * status); an OK sequence with a non-finite weight makes the entries it touches non-finite -- in
+ * b_cnt the entries (j, v) of the values v it observes; weight 0 adds only +-0.  The outputs are
+ * overwritten, not accumulated (nseq = 0 writes zeros to the three arrays).
+ * b_cnt is exactly 0 wherever b[j][v] = -inf, for every v no element of an OK sequence observes
+ * (a value only a BADOBS or INFEASIBLE sequence holds counts nothing), and for the states a forced
+ * tag excludes at its element.
+ * How: the backward pass is the gradient arm's; its rows w_s gamma go to gamma_out's device array
+ * or, without one, to a chunk-local workspace.  Per chunk the rows are keyed by observation (rows
+ * of sequences that are not OK, and observations outside [0, V), get a discard key and are never
+ * read), stable-sorted by key, and the sorted list is cut into fixed parts; a run is a maximal
+ * stretch of one key inside one part.  One wave per part and 128 columns adds the rows of each
+ * run in sorted order and stores the run's sum whole; the runs of each v are then added in
+ * ascending order into a [V][NP] accumulator, chunks in stream order, and a last kernel writes the
+ * compact state-major array.  No atomic adds.  Results are therefore bit-identical between two
+ * calls with the same arguments on the same handle state and between the host and device
+ * variants; they are NOT bit-identical across chunk plans (workspace_bytes), part sizes of the
+ * gather (tuning key bcnt_part_rows) or of the count GEMM (xi_part_rows), which regroup the sums
+ * -- the bounds hold for all of them.
+ * Numerics, with u = 2^-53, T the longest sequence of the call, L its elements, and b_abs the
+ * same statistic computed with |w_s| in place of w_s:
+ *   |b_cnt - exact| <= (4 T (N + 8) + L + 1) u b_abs + 1e-290 L max(1, max |w|).
+ * 4 T (N + 8) u: gamma's bound (cv_posterior_batch); + 1: the product with the weight; + L: a sum
+ * of n signed terms gains at most (n - 1) u of the sum of their magnitudes in whatever grouping
+ * (runs, then their fold, then the chunks), and no entry has more than L terms; 1e-290 per term
+ * for what underflows in gamma (DESIGN.md "Emission counts").  pi_cnt and a_cnt hold the bounds of
+ * cv_expected_counts (weight null) and of cv_loglik_grad_emissions' pi_grad and a_grad (weights).
+ * opts, limits (N <= 4096), statuses and the CV_EINFEASIBLE-after-writing rule are those of
+ * cv_expected_counts.  A null pi_cnt_out, a_cnt_out or b_cnt_out is CV_EINVAL.  Workspace: that of
+ * cv_expected_counts, plus 8 NP bytes per element of a chunk without gamma_out, all under
+ * workspace_bytes; beside it, on the handle, the [V][NP] accumulator (8 V NP bytes; CV_ENOMEM when
+ * it cannot be allocated), 20 bytes per element of a chunk and the sort's scratch, and 8 NP + 4
+ * bytes per run (at most parts + min(V + 1, rows) runs per chunk).  A chunk of more than INT32_MAX
+ * elements is CV_ELIMIT.  cv_hmm_release_workspaces frees all of it.  cv_last_timing: bt_ms
+ * covers the emission-count kernels too.  Host pointers; synchronous. */
+CV_API cv_status cv_expected_counts_model(cv_hmm* h, int64_t nseq, const int64_t* offsets, const int32_t* obs,
+                                          const double* weight /*[nseq], nullable = all 1*/, const cv_opts* opts,
+                                          double* loglik_out /*[nseq]*/, double* pi_cnt_out /*[N]*/,
+                                          double* a_cnt_out /*[N*N] from-major*/,
+                                          double* b_cnt_out /*[N*V], b's own layout*/,
+                                          double* gamma_out /*nullable [L*N]: w_s gamma*/,
+                                          uint8_t* status_out /*[nseq]*/);
+/* The same on device-resident buffers, with cv_expected_counts_device's contract: enqueued on
+ * opts->stream (or the handle's stream), returns after enqueueing; weight_dev (nullable) and
+ * gamma_dev (nullable) are device pointers.  This is the backward pass of
+ * cviterbi.autograd.discrete_loglik with weight_dev = grad_output. */
+CV_API cv_status cv_expected_counts_model_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
+                                                 const int64_t* offsets_dev, const int32_t* obs_dev,
+                                                 const double* weight_dev, const cv_opts* opts, double* loglik_dev,
+                                                 double* pi_cnt_dev, double* a_cnt_dev, double* b_cnt_dev,
+                                                 double* gamma_dev, uint8_t* status_dev);
 
 /* ---- trait Solver (viterbi_solver.rs:11-16) -------------------------------------------
  * kind: "gpu"      f32 trellis kernel, VITERBI association, f64 re-scored objective
