@@ -1,4 +1,6 @@
-// cviterbi.cpp -- C ABI (include/cviterbi.h) over the MI355X trellis kernels.
+// cviterbi.cpp -- C ABI (include/cviterbi.h) over the MI355X trellis kernels: the handle (its
+// struct is in handle.hpp), decode, K-best, constrained decode, chain, fit and solver entries.  The
+// posterior / sampling / counts / gradient entries are in evaluate.cpp.
 //
 // Host side of the drop-in boundary: the HMM handle mirrors struct HMM<D> and its
 // log-prob lookups (src/hmm/hmm.rs:10-18, 207-245), the batch decode replaces the
@@ -39,32 +41,16 @@
 #include "kernels/fit.h"
 #include "kernels/emis.h"
 #include "kernels/kbest.h"
-#include "kernels/bcount.h"
-#include "kernels/posterior.h"
-#include "kernels/sample.h"
 #include "kernels/trellis.h"
 #include "kernels/trellis64.h"
+#include "handle.hpp"
 #include "tuning.h"
 
-namespace {
+using namespace cvi;
+
+namespace cvi {
 
 thread_local std::string g_err;
-
-// the handle's lock plus its tuning snapshot as the calling thread's current tuning (tuning.h)
-#define CV_LOCK(h)                             \
-  std::lock_guard<std::mutex> lk((h)->mu);     \
-  cvk::TuningScope tuning_scope((h)->tuning)
-
-inline uint64_t dbits(double x) {
-  uint64_t b;
-  std::memcpy(&b, &x, 8);
-  return b;
-}
-inline double from_dbits(uint64_t b) {
-  double x;
-  std::memcpy(&x, &b, 8);
-  return x;
-}
 
 cv_status set_err(cv_status st, const char* fmt, ...) {
   char buf[512];
@@ -76,54 +62,7 @@ cv_status set_err(cv_status st, const char* fmt, ...) {
   return st;
 }
 
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t _e = (expr);                                                                    \
-    if (_e != hipSuccess)                                                                      \
-      return set_err(CV_EDEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, \
-                     __LINE__);                                                                \
-  } while (0)
-
-// device bytes this process's library holds now / at most (cv_device_memory)
 std::atomic<int64_t> g_dev_cur{0}, g_dev_peak{0};
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { release(); }
-  void release() {
-    if (p) {
-      (void)hipFree(p);
-      g_dev_cur -= (int64_t)bytes;
-    }
-    p = nullptr;
-    bytes = 0;
-  }
-  cv_status ensure(size_t n) {
-    if (n <= bytes && p) return CV_OK;
-    release();
-    if (n == 0) n = 16;
-    hipError_t e = hipMalloc(&p, n);
-    if (e != hipSuccess) {
-      p = nullptr;
-      (void)hipGetLastError();
-      return set_err(CV_ENOMEM, "hipMalloc(%zu) failed: %s", n, hipGetErrorString(e));
-    }
-    bytes = n;
-    const int64_t cur = g_dev_cur += (int64_t)n;
-    int64_t pk = g_dev_peak.load();
-    while (cur > pk && !g_dev_peak.compare_exchange_weak(pk, cur)) {
-    }
-    return CV_OK;
-  }
-  template <typename T>
-  T* as() const {
-    return static_cast<T*>(p);
-  }
-};
 
 cv_status upload(DevBuf& buf, const void* src, size_t bytes) {
   cv_status st = buf.ensure(bytes);
@@ -132,287 +71,6 @@ cv_status upload(DevBuf& buf, const void* src, size_t bytes) {
   return CV_OK;
 }
 
-constexpr uint64_t kDefaultWorkspace = 8ull << 30;
-constexpr uint64_t kDefaultWorkspaceT64 = 64ull << 30;  // config 5 resume decode in one chunk: 3% faster than 40 GiB
-constexpr size_t kMaxTimedEvents = 1 << 16;  // cv_timing_begin: at most 16,384 chunk launches timed
-
-}  // namespace
-
-// Pinned, double-buffered host staging of a decode call's longest-first order: the call
-// writes slot k only after that slot's previous copy has completed (its event), so the
-// copy is truly asynchronous and the host never waits for the stream's earlier work
-// A grow-only pinned host buffer (hipHostMalloc) for small device-to-host results read right
-// after a synchronize (the parallel chain's scores, statuses and certificates: two direct
-// copies instead of three through the runtime's pageable staging).
-struct PinnedHost {
-  void* p = nullptr;
-  size_t cap = 0;
-  PinnedHost() = default;
-  PinnedHost(const PinnedHost&) = delete;
-  PinnedHost& operator=(const PinnedHost&) = delete;
-  ~PinnedHost() { release(); }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  bool ensure(size_t bytes) {
-    if (cap >= bytes && p) return true;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-    const size_t want = std::max<size_t>(bytes, 4096);
-    if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) {
-      (void)hipGetLastError();
-      return false;
-    }
-    cap = want;
-    return true;
-  }
-  template <typename T>
-  T* as() const { return static_cast<T*>(p); }
-};
-
-struct OrderStage {
-  int32_t* p[2] = {nullptr, nullptr};
-  size_t cap[2] = {0, 0};
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  bool pending[2] = {false, false};
-  int slot = 0;
-  OrderStage() = default;
-  OrderStage(const OrderStage&) = delete;
-  OrderStage& operator=(const OrderStage&) = delete;
-  ~OrderStage() {
-    for (int k = 0; k < 2; ++k) {
-      if (pending[k]) (void)hipEventSynchronize(ev[k]);
-      if (p[k]) (void)hipHostFree(p[k]);
-      if (ev[k]) (void)hipEventDestroy(ev[k]);
-    }
-  }
-  // the current slot, at least n entries, free to write (nullptr: allocation failed)
-  int32_t* acquire(size_t n) {
-    const int k = slot;
-    if (pending[k]) {
-      if (hipEventSynchronize(ev[k]) != hipSuccess) return nullptr;
-      pending[k] = false;
-    }
-    if (!ev[k] && hipEventCreateWithFlags(&ev[k], hipEventDisableTiming) != hipSuccess) return nullptr;
-    if (cap[k] < n) {
-      if (p[k]) (void)hipHostFree(p[k]);
-      p[k] = nullptr;
-      cap[k] = 0;
-      const size_t want = std::max<size_t>(n, 4096);
-      if (hipHostMalloc((void**)&p[k], want * 4, hipHostMallocDefault) != hipSuccess) return nullptr;
-      cap[k] = want;
-    }
-    return p[k];
-  }
-  // after the copy out of the current slot is enqueued on `stream`
-  hipError_t release(hipStream_t stream) {
-    const hipError_t e = hipEventRecord(ev[slot], stream);
-    pending[slot] = e == hipSuccess;
-    slot ^= 1;
-    return e;
-  }
-};
-
-struct cv_hmm {
-  int N = 0, D = 0;
-  std::vector<int64_t> bdims;
-  int64_t V = 0;
-  std::vector<double> pi, a, b;  // host log10, canonical (-0.0 -> +0.0); b state-major [N*V]
-  int device = 0;
-  int cus = 0;                      // compute units of the device (workgroup rounds)
-  hipStream_t stream = nullptr;     // default stream of the handle
-  hipStream_t bt_stream = nullptr;  // backtrack stream (overlaps the next chunk's forward)
-  std::mutex mu;
-  // tuning keys and test hooks (tuning.h): the environment at cv_hmm_create, then
-  // cv_hmm_set_tuning only; every locked host API call makes it the thread's current tuning
-  cvk::Tuning tuning;
-
-  // trellis kernel tables (f32, padded to NP)
-  int np = 0;
-  DevBuf t_aimg, t_pi, t_et, t_at, t_arm;  // t_arm: row-major A (one-wave kernel)
-  // one-wave kernel (N <= 64): tables padded to npw = 16 * ceil(N / 16) states
-  int npw = 0;
-  DevBuf w_arm, w_pi, w_et, w_at;
-  DevBuf t_aimg_T, t_pi0;  // reversed (backward) pass: VALU image of a^T, pi = 0
-  // f64 tables (generic f64 kernel + re-scoring): pi[N], a[N*N], et[V][N]
-  bool f64_ready = false;
-  DevBuf d_pi64, d_a64, d_et64;
-  DevBuf d_at64;  // [N][N] a^T, f64: the constrained decode's suffix pass for N > 256
-
-  // exact-f64 trellis tables (trellis_fwd_f64 / backtrack_f64), padded to np64 = 64*ceil(N/64)
-  int np64 = 0;
-  bool t64_ready = false;
-  DevBuf q_a, q_at, q_pi, q_et;
-  DevBuf q_at32;            // f32(a^T), uploaded when t64_nonpos
-  bool t64_nonpos = false;  // every finite pi/a/b entry in [-2^80, 0] (NONPOS backtrack test)
-  int nonpos_cache = -1;    // model_nonpos(): the same predicate without the t64 tables (any N)
-  double arc_max = -1.0;    // max finite |pi| or |a|, plus max finite |b| (< 0: not computed yet)
-  double cert_rho_cap = 0.0;  // the parallel chain's certified backtrack (T64BtArgs::rho_cap)
-  // sparse low planes (tuning key t64_lo_every): the resolver's device counter block
-  // ([kT64StatSlots + 1][kT64StatWords] u64; the last slot holds the call's lo_every and
-  // sequence count) and its pinned host copy, made asynchronously after each plain batch decode
-  // on the f64 trellis, so it holds the last such call that has FINISHED.  t64_lo_off: the
-  // sticky guard -- a call that replayed densely more than once per 64 sequences (tie-heavy
-  // models) or failed a self-check pins the handle to full rows
-  DevBuf t64_stats;
-  PinnedHost t64_stats_pin;
-  bool t64_lo_off = false;
-  // certified fixed-point first pass (tuning key t64_fixed_first, fixed_first_decode): the int32
-  // tables in the f32 trellis tables' layouts, built once per handle (fx_state -1: not looked at
-  // yet, 0: the model is outside the pass's range, 1: ready); the per-sequence certificates and
-  // their pinned host copy; the compact batch of the uncertified sequences.  fx_pinned: the
-  // sticky guard -- a call that left more than 1 in 8 sequences uncertified pins the handle to
-  // the f64 kernels.  fx_last: engaged, certified, fallback, pinned (cv_last_fixed_first_stats)
-  int fx_state = -1;
-  DevBuf fx_aimg, fx_pi, fx_et, fx_at;
-  double fx_gain = 0.0;
-  DevBuf fx_cert, fx_idx, fx_obs2, fx_path2, fx_score2, fx_status2;
-  PinnedHost fx_cert_pin;
-  std::vector<int64_t> fx_idx_host;
-  bool fx_pinned = false;
-  int64_t fx_last[4] = {0, 0, 0, 0};
-  // certified f32 round-up first pass (tuning key t64_f32ru_first): the shifted, rounded-up f32
-  // tables in the same layouts, the shifts ca [N] and cb [V] in f64 (ru_state as fx_state); the
-  // shifts mu_t and losing candidates r_t per element and E per sequence of the last call.
-  // fx_last_kind: which first pass the last call took (0 none, 1 integer, 2 round-up)
-  int ru_state = -1;
-  DevBuf ru_aimg, ru_pi, ru_et, ru_at, ru_ca, ru_cb;
-  double ru_ks = 0.0;
-  DevBuf ru_mu, ru_r, ru_e;
-  int fx_last_kind = 0;
-  DevBuf q_pi0;  // the reversed (suffix) pass: pi = 0 for the N states, -inf padding
-  // f32 generic tables
-  bool g32_ready = false;
-  DevBuf d_pi32, d_a32, d_et32;
-  DevBuf d_at32;  // [N][N] a^T f32 (generic_bt_rows)
-  // probability-space tables of the posterior kernels (10^x, zero padded to pnp states; built on
-  // first use): pi[pnp], a[pnp][pnp], a^T, et[V][pnp], and the dump rows of masked stores
-  int pnp = 0;
-  DevBuf p_pi, p_a, p_at, p_et, p_dump;
-  // posterior workspace: the scaled forward rows of one chunk, the longest-first order, and the
-  // host API's gamma staging
-  DevBuf ps_rows, ps_order, st_gamma;
-  DevBuf ps_kshift;  // cv_posterior_emissions*: each sequence's sum of row-scale exponents (int64)
-  // cv_expected_counts*: the GEMM's partial tiles, the call's NP x NP accumulator, gamma_0 of every
-  // sequence, and the host API's staging of pi_cnt [N] and a_cnt [N][N]
-  DevBuf ps_xi_part, ps_xi_s, ps_g0, st_cnt;
-  DevBuf ps_bc_acc, ps_bc_sort, ps_bc_part;  // cv_expected_counts_model*: [V][NP] accumulator, sort scratch, run sums
-  PinnedHost sm_pin;  // cv_sample_batch: the log-likelihoods and score planes on their way to the caller
-  OrderStage ps_pin;
-  // K-best workspace: the u16 back-pointers of one chunk, each sequence's last lists, the
-  // longest-first order, the ranks' end points, and the host API's count staging
-  DevBuf kb_bp, kb_last, kb_order, kb_end, st_count;
-  OrderStage kb_pin;
-  // workspace
-  DevBuf ws_main, ws_last, ws_order;
-  // a second decode workspace + stream: the constrained decode's unconstrained sequences run
-  // on it beside the terms pass (constrained decode)
-  struct SideWs {
-    DevBuf main, last, order, idx, obs2, path2, res2;
-    std::vector<int32_t> order_host;
-    OrderStage order_pin;
-    hipEvent_t ws_done = nullptr;  // the last decode_device call on this workspace has finished
-    bool ws_rec = false;
-    std::vector<int64_t> idx_host;
-    std::vector<hipEvent_t> ev;
-    hipStream_t stream = nullptr;  // lowest priority: fills what the constrained work leaves idle
-    hipStream_t hi = nullptr;      // highest priority: the constrained work itself
-    hipEvent_t start = nullptr, done = nullptr, after = nullptr;
-  } side;
-  DevBuf st_off, st_obs, st_path, st_score, st_status, st_forced;
-  DevBuf st_emis;  // cv_decode_emissions: the host array's rows, compact ([elements][N])
-  DevBuf cs_ranges, cs_delta, cs_g, cs_mu, cs_start, cs_zero, cs_queue;  // constrained-decode scratch
-  DevBuf cs_wrows;  // the wide generic_ext's rows ([slot][2][N], N > 10,240)
-  DevBuf cs_comp, cs_words;  // device exact unary sums: per-sequence components, output words
-  DevBuf cs_flag;            // device exact sums: out-of-range term flag
-  DevBuf cs_seg;             // segment-table rows (cs_delta keeps the prefix rows t_1)
-  // resume flow of the constrained decode: stored prefix rows, forced row t_1 per constrained
-  // sequence, the compact suffix batch and its index arrays
-  DevBuf rs_rows, rs_rowbase, rs_resume, rs_start, rs_off2, rs_ridx, rs_slot, rs_obs2, rs_frc2, rs_path2;
-  // certified suffix trace (f64): the suffix pass's rows, their per-slot bases, the slot flags
-  DevBuf rs_srows, rs_srowbase, rs_cert;
-  hipEvent_t rs_ev = nullptr;  // prefix backtrack done / staging done
-  std::vector<int32_t> order_host;
-  OrderStage order_pin;
-  // the last decode_device call on the main workspace has finished (recorded on its stream;
-  // the next call waits for it on ITS stream, so calls on different streams never share the
-  // workspace while it is in use)
-  hipEvent_t ws_done = nullptr;
-  bool ws_rec = false;
-  std::vector<float> host_dl, host_mu;  // constrained-decode term rows (kept: no per-call page faults)
-  std::vector<int64_t> sort_pos;        // counting-sort buckets of the longest-first order
-  // timing events of the last call
-  std::vector<hipEvent_t> ev;  // 4 per chunk: fwd start/end (main stream), bt start/end
-  std::vector<uint8_t> ev_nobt;  // per chunk of ev: nothing ran between its bt events (bt_ms reads 0)
-  int64_t last_launches = 0;
-  size_t last_ev_base = 0;  // first event of the last call in ev
-  // cv_timing_begin/end: every decode call's events kept (appended) until cv_timing_end
-  bool acc_on = false, acc_overflow = false;
-  size_t acc_used = 0;
-  int32_t last_kernel = 0;
-  int32_t last_np = 0;
-  int32_t last_mt = -1;
-  uint64_t last_explored = 0;
-  int64_t last_traced = 0;  // constrained sequences the last resume flow certified (suffix trace)
-  // the last cv_decode_superseq_cp: parallel chain ran (1/0), sequences certified, sequences in
-  // serial-chain runs, runs, certified folds done by the quantised sum, sequences taken from
-  // speculative parallel re-decodes, such batches
-  // speculative parallel re-decodes, such batches, candidate paths fetched packed for the walk,
-  // walk steps that waited for the whole path copy
-  int64_t last_chain[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  // the parallel chain's per-call device arrays, kept between calls (grow-only): a
-  // config-4-sized call allocated and freed ~0.4 GB of them each time (hipFree synchronises)
-  struct ChainBufs {
-    DevBuf off, obs, path, res, cert, ebin, q, ends, gid, gpath;
-    // serial runs and speculative batches (kept, so no hipFree -- a device-wide sync -- lands
-    // while the second part's forward pass runs)
-    DevBuf first, rpsi, rows, small, rpath, soff, sobs, spath, sres, sinit, slast, spsi;
-  } chainb;
-  // the chain's own stream (high priority: its walk-side kernels -- end states, quantised folds,
-  // gathers, runs, speculative batches -- run beside the second part's forward pass) and the
-  // events closing each part's decode
-  hipStream_t chain_stream = nullptr;
-  std::vector<hipEvent_t> part_ev;
-  // the parallel chain's path copy: per decode chunk, behind that chunk's backtrack (chunk_ev),
-  // on a non-blocking stream of its own, from a host thread of its own
-  std::vector<hipEvent_t> chunk_ev;
-  std::vector<hipEvent_t> emis_ev;  // dense emissions: chunk k's rows staged (on bt_stream, beside chunk k-1)
-  hipStream_t copy_stream = nullptr;
-  PinnedHost chain_pin;  // the chain's scores, statuses and certificates on their way to the host
-  PinnedHost chain_gpin;  // the chain's gathered candidate paths and speculative results (16 MiB)
-  // the chain's later parts' observations and its path copy's two-chunk ring, staged through
-  // pinned memory: the DMA engines move them, where a pageable copy runs blit kernels beside
-  // the forward passes (tuning keys chain_pin_obs / chain_pin_path)
-  PinnedHost chain_obs_pin, chain_ring[2];
-  hipEvent_t ring_ev[2] = {nullptr, nullptr};
-
-  ~cv_hmm() {
-    for (auto e : ring_ev)
-      if (e) (void)hipEventDestroy(e);
-    for (auto e : ev) (void)hipEventDestroy(e);
-    for (auto e : side.ev) (void)hipEventDestroy(e);
-    if (side.start) (void)hipEventDestroy(side.start);
-    if (side.done) (void)hipEventDestroy(side.done);
-    if (side.after) (void)hipEventDestroy(side.after);
-    if (side.stream) (void)hipStreamDestroy(side.stream);
-    if (side.hi) (void)hipStreamDestroy(side.hi);
-    if (rs_ev) (void)hipEventDestroy(rs_ev);
-    if (ws_done) (void)hipEventDestroy(ws_done);
-    if (side.ws_done) (void)hipEventDestroy(side.ws_done);
-    if (stream) (void)hipStreamDestroy(stream);
-    if (bt_stream) (void)hipStreamDestroy(bt_stream);
-    for (auto e : chunk_ev) (void)hipEventDestroy(e);
-    for (auto e : emis_ev) (void)hipEventDestroy(e);
-    for (auto e : part_ev) (void)hipEventDestroy(e);
-    if (copy_stream) (void)hipStreamDestroy(copy_stream);
-    if (chain_stream) (void)hipStreamDestroy(chain_stream);
-  }
-};
-
-namespace {
 
 // Device bytes free right now plus `held` (buffers the caller is about to re-size); 0 when the
 // runtime cannot tell.
@@ -447,6 +105,23 @@ cv_status set_device(cv_hmm* h) {
   if (!h->stream) HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
   if (!h->bt_stream) HIP_TRY(hipStreamCreateWithFlags(&h->bt_stream, hipStreamNonBlocking));
   return CV_OK;
+}
+
+}  // namespace cvi
+
+namespace {
+
+constexpr size_t kMaxTimedEvents = 1 << 16;  // cv_timing_begin: at most 16,384 chunk launches timed
+
+inline uint64_t dbits(double x) {
+  uint64_t b;
+  std::memcpy(&b, &x, 8);
+  return b;
+}
+inline double from_dbits(uint64_t b) {
+  double x;
+  std::memcpy(&x, &b, 8);
+  return x;
 }
 
 float f32(double x) { return (float)x; }
@@ -521,7 +196,9 @@ cv_status ensure_trellis_tables(cv_hmm* h) {
   return CV_OK;
 }
 
-cv_status ensure_f64_tables(cv_hmm* h) {
+}  // namespace
+
+cv_status cvi::ensure_f64_tables(cv_hmm* h) {
   if (h->f64_ready) return CV_OK;
   const int N = h->N;
   const int64_t V = h->V;
@@ -535,6 +212,8 @@ cv_status ensure_f64_tables(cv_hmm* h) {
   h->f64_ready = true;
   return CV_OK;
 }
+
+namespace {
 
 // a^T [N][N] f64 (generic_ext's suffix pass, generic_bt_rows), uploaded on first use
 cv_status ensure_at64(cv_hmm* h) {
@@ -678,49 +357,6 @@ void trace_mark(const char* what) {
   last = now;
 }
 
-// Host worker threads for the O(elements) loops of the host API (validation, constraint
-// bookkeeping, exact accumulation): min(16, hardware threads), tuning key host_threads overrides.
-int host_threads() {
-  static const int hw = (int)std::thread::hardware_concurrency();
-  const int v = cvk::tuning().host_threads > 0 ? cvk::tuning().host_threads : hw;
-  return std::max(1, std::min(v > 0 ? v : 1, 16));
-}
-
-// f(t, lo, hi) over [0, n) split into contiguous ranges, one per worker (t = worker index).
-template <typename F>
-void parallel_ranges(int64_t n, F&& f, int64_t min_per_thread = 1 << 16) {
-  const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(host_threads(), n / std::max<int64_t>(min_per_thread, 1)));
-  if (nt <= 1) {
-    f(0, (int64_t)0, n);
-    return;
-  }
-  std::vector<std::thread> th;
-  th.reserve(nt);
-  for (int t = 0; t < nt; ++t) th.emplace_back([&, t] { f(t, n * t / nt, n * (t + 1) / nt); });
-  for (auto& x : th) x.join();
-}
-
-// First index k in [lo, hi) with bad(k), or -1 (parallel scan; the smallest index wins).
-template <typename P>
-int64_t first_bad(int64_t lo, int64_t hi, P&& bad) {
-  std::vector<int64_t> first((size_t)host_threads(), -1);
-  parallel_ranges(hi - lo, [&](int t, int64_t a, int64_t b) {
-    for (int64_t k = lo + a; k < lo + b; ++k)
-      if (bad(k)) {
-        first[t] = k;
-        return;
-      }
-  });
-  for (int64_t f : first)
-    if (f >= 0) return f;  // workers hold ascending ranges
-  return -1;
-}
-
-cv_status check_batch(int64_t nseq, const int64_t* offsets) {
-  char msg[64];
-  return cvplan::check_offsets(nseq, offsets, msg) ? CV_OK : set_err(CV_EINVAL, "%s", msg);
-}
-
 hipEvent_t get_event(std::vector<hipEvent_t>& ev, size_t i) {
   while (ev.size() <= i) {
     hipEvent_t e;
@@ -730,8 +366,30 @@ hipEvent_t get_event(std::vector<hipEvent_t>& ev, size_t i) {
   return ev[i];
 }
 
-// ---- scaffolding shared by the device cores (decode_device, posterior_device, kbest_device) ----
-// The host copy of the offsets, checked: the caller's, or fetched from the device into `off_copy`.
+}  // namespace
+
+namespace cvi {
+
+// Host worker threads for the O(elements) loops of the host API (validation, constraint
+// bookkeeping, exact accumulation): min(16, hardware threads), tuning key host_threads overrides.
+int host_threads() {
+  static const int hw = (int)std::thread::hardware_concurrency();
+  const int v = cvk::tuning().host_threads > 0 ? cvk::tuning().host_threads : hw;
+  return std::max(1, std::min(v > 0 ? v : 1, 16));
+}
+
+cv_status check_batch(int64_t nseq, const int64_t* offsets) {
+  char msg[64];
+  return cvplan::check_offsets(nseq, offsets, msg) ? CV_OK : set_err(CV_EINVAL, "%s", msg);
+}
+
+cv_status report_infeasible(int64_t nseq, const uint8_t* status, const char* what) {
+  for (int64_t s = 0; s < nseq; ++s)
+    if (status[s] == CV_SEQ_INFEASIBLE) return set_err(CV_EINFEASIBLE, "sequence %lld %s", (long long)s, what);
+  return CV_OK;
+}
+
+// ---- scaffolding shared by the device cores (described at its declarations in handle.hpp) ----
 cv_status host_offsets(int64_t nseq, const int64_t*& offsets_host, const int64_t* offsets_dev,
                        std::vector<int64_t>& off_copy, hipStream_t stream) {
   if (!offsets_host && nseq >= 0) {
@@ -743,7 +401,6 @@ cv_status host_offsets(int64_t nseq, const int64_t*& offsets_host, const int64_t
   return check_batch(nseq, offsets_host);
 }
 
-// The longest-first order of a call on its way to the device, through the pinned stage.
 cv_status upload_order(DevBuf& dev, OrderStage& stage, const int32_t* order_host, int64_t nseq, hipStream_t stream,
                        const int32_t** order_dev) {
   cv_status st = dev.ensure((size_t)nseq * 4);
@@ -757,9 +414,6 @@ cv_status upload_order(DevBuf& dev, OrderStage& stage, const int32_t* order_host
   return CV_OK;
 }
 
-// The nev timing events of a call, evv[*eb ...]: from 0 (each call overwrites the last), or
-// appended after the calls already timed since cv_timing_begin.  side_ws: the side workspace's
-// own events, no bookkeeping.
 cv_status reserve_events(cv_hmm* h, bool side_ws, size_t nev, size_t* eb) {
   if (!side_ws && h->acc_on && h->acc_used + nev > kMaxTimedEvents) h->acc_on = false, h->acc_overflow = true;
   *eb = (!side_ws && h->acc_on) ? h->acc_used : 0;
@@ -774,8 +428,6 @@ cv_status reserve_events(cv_hmm* h, bool side_ws, size_t nev, size_t* eb) {
   return CV_OK;
 }
 
-// The end of a core call whose last work is on `stream`: its nev events are kept (cv_timing_begin)
-// and the workspace's ws_done follows it.
 cv_status end_call(cv_hmm* h, bool side_ws, size_t nev, hipStream_t stream) {
   if (!side_ws && h->acc_on) h->acc_used += nev;
   hipEvent_t& ws_done = side_ws ? h->side.ws_done : h->ws_done;
@@ -785,12 +437,9 @@ cv_status end_call(cv_hmm* h, bool side_ws, size_t nev, hipStream_t stream) {
   return CV_OK;
 }
 
-// Caller-supplied emission scores (cv_decode_emissions*): a dense device array, row e (element
-// index of the CSR offsets) at p + e * ld, N log10 scores each.
-struct EmisSrc {
-  const double* p;
-  int64_t ld;
-};
+}  // namespace cvi
+
+namespace {
 
 // What a decode kernel reads its emissions through: row et + obs[e] * stride, obs[e] < nobs.
 struct EmisView {
@@ -1430,416 +1079,6 @@ cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, co
   return end_call(h, side_ws, nev, stream);
 }
 
-// ---- posterior (sum-product) path: cv_posterior_batch* --------------------------------------
-// Probability-space tables of the posterior kernels: p = 10^x by the host's correctly rounded
-// pow (-inf -> 0 exactly), zero padded to pnp states so the kernels never test a row or column
-// against N; the emission column of each observation is contiguous ([V][pnp]).
-cv_status ensure_post_tables(cv_hmm* h) {
-  const int np = cvp::post_padded_states(h->N);
-  if (h->pnp == np) return CV_OK;
-  const int N = h->N;
-  const int64_t V = h->V;
-  auto p10 = [](double x) { return x == -INFINITY ? 0.0 : std::pow(10.0, x); };
-  std::vector<double> pi((size_t)np, 0.0), a((size_t)np * np, 0.0), at((size_t)np * np, 0.0), et((size_t)V * np, 0.0);
-  for (int i = 0; i < N; ++i) pi[(size_t)i] = p10(h->pi[(size_t)i]);
-  parallel_ranges(N, [&](int, int64_t lo, int64_t hi) {
-    for (int64_t i = lo; i < hi; ++i)
-      for (int j = 0; j < N; ++j) {
-        const double v = p10(h->a[(size_t)i * N + j]);
-        a[(size_t)i * np + j] = v;
-        at[(size_t)j * np + i] = v;
-      }
-  }, std::max<int64_t>(1, 4096 / N));
-  parallel_ranges(N, [&](int, int64_t lo, int64_t hi) {
-    for (int64_t i = lo; i < hi; ++i)
-      for (int64_t o = 0; o < V; ++o) et[(size_t)o * np + i] = p10(h->b[(size_t)i * V + o]);
-  }, std::max<int64_t>(1, 4096 / std::max<int64_t>(V, 1)));
-  cv_status st;
-  if ((st = upload(h->p_pi, pi.data(), pi.size() * 8)) != CV_OK) return st;
-  if ((st = upload(h->p_a, a.data(), a.size() * 8)) != CV_OK) return st;
-  if ((st = upload(h->p_at, at.data(), at.size() * 8)) != CV_OK) return st;
-  if ((st = upload(h->p_et, et.data(), et.size() * 8)) != CV_OK) return st;
-  if ((st = h->p_dump.ensure((size_t)cvp::kPostDumpWaves * 64 * 8)) != CV_OK) return st;
-  h->pnp = np;
-  return CV_OK;
-}
-
-// What the posterior path accepts of the options and the model (no device needed).
-cv_status posterior_opts_ok(const cv_hmm* h, const cv_opts& o) {
-  if (o.dtype == CV_DTYPE_F32) return set_err(CV_EUNSUPPORTED, "the posterior path is f64 only");
-  if (o.dtype != CV_DTYPE_F64) return set_err(CV_EINVAL, "bad dtype %d", o.dtype);
-  if (o.assoc != CV_ASSOC_VITERBI)
-    return set_err(CV_EINVAL, "the posterior path reads the model as the VITERBI association (assoc %d)", o.assoc);
-  if (o.kernel != CV_KERNEL_AUTO && o.kernel != CV_KERNEL_GENERIC)
-    return set_err(CV_EINVAL, "posterior kernel must be AUTO or GENERIC (kernel %d)", o.kernel);
-  if (h->N > cvp::kPostMaxStates)
-    return set_err(CV_EUNSUPPORTED, "the posterior kernels cover N <= %d (N=%d)", cvp::kPostMaxStates, h->N);
-  return CV_OK;
-}
-
-// cv_sample_batch*: what the sampler puts in place of the backward pass of a chunk (sample_device)
-struct SampleReq {
-  int32_t draws;
-  uint64_t seed;
-  int64_t seq_base;
-  int32_t* path;  // device, [draws][offsets[nseq]]
-  double* score;  // device, [draws][nseq], nullable
-};
-// cv_expected_counts*: the counts arm of the backward pass and the kernels behind it
-struct CountsReq {
-  double* pi_cnt;  // device, [N]
-  double* a_cnt;   // device, [N][N]
-  // cv_loglik_grad_emissions*: the gradient arm (grad.hip) -- every term times its sequence's weight,
-  // the gamma rows (then the gradient of E) at the caller's stride; gamma_dev is null in such a call
-  bool grad = false;
-  const double* weight = nullptr;  // device, [nseq]; null: all 1
-  double* egrad = nullptr;         // device, nullable, row e at egrad + e * ld_grad
-  int64_t ld_grad = 0;
-  // cv_expected_counts_model*: the expected emission counts of the discrete model (bcount.hip), with
-  // grad set -- the rows w_s gamma the gradient arm stores are what the scatter by observation adds.
-  // egrad (ld_grad = N) is then the caller's gamma; null: a chunk-local workspace takes the rows
-  double* b_cnt = nullptr;  // device, nullable, [N][V]
-};
-
-// Core of cv_posterior_batch*: all pointers are device pointers except offsets_host.  Chunks of
-// whole sequences (original order) whose forward rows fit the workspace cap run forward then
-// backward on `stream`; scoring mode (no path, no gamma) is one forward launch with no rows.
-// emis (cv_posterior_emissions*): the emissions of every element come from this dense array
-// of log10 scores instead of the handle's b through obs_dev (ignored, may be null).  Each chunk's
-// rows are staged in probability space behind its forward rows (emis_prepare_lin_f64: 8 NP + 4
-// bytes per element more, under the same cap -- so the scoring mode is chunked too) and stay
-// there until its backward pass has run; the sequences' row-scale exponents go to ps_kshift.
-// smp (cv_sample_batch*): the rows are stored and each chunk's backward pass is replaced by the
-// sampler's walk and the scores of its paths; everything else -- planning, order, events -- is
-// this function's, so a sampling call chunks and times exactly like a posterior call.
-// cnt (cv_expected_counts*): the backward pass runs with its counts arm (8 NP + 8 bytes per
-// element more: the U row and 1 / rsum), each chunk's rows then go through the count GEMM and its
-// fold into ps_xi_s (zeroed here), and the last chunk is followed by the kernels that write
-// pi_cnt and a_cnt -- all inside the chunk's backward events, so bt_ms covers them.  With cnt->grad
-// (cv_loglik_grad_emissions*) the backward pass is the gradient arm's; nothing else differs.
-// cnt->b_cnt (cv_expected_counts_model*; with cnt->grad, the handle's own b): the rows w_s gamma of
-// the gradient arm go to cnt->egrad (the caller's gamma, stride N) or, when that is null, to a
-// chunk-local workspace (8 NP bytes per element more, under the cap); after each chunk's count GEMM
-// the rows are added by observation into ps_bc_acc (zeroed here; bcount.hip: keys, stable sort,
-// run sums, fold), and the last chunk is followed by the kernel that writes b_cnt.
-cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, const int64_t* offsets_dev,
-                           const int32_t* obs_dev, const cv_opts& o, double* loglik_dev, int32_t* path_dev,
-                           double* gamma_dev, uint8_t* status_dev, hipStream_t stream, const EmisSrc* emis = nullptr,
-                           const SampleReq* smp = nullptr, const CountsReq* cnt = nullptr) {
-  cv_status st = posterior_opts_ok(h, o);
-  if (st != CV_OK) return st;
-  if (smp && smp->score && (st = ensure_f64_tables(h)) != CV_OK) return st;
-  const bool generic = o.kernel == CV_KERNEL_GENERIC || h->N > cvp::kPostMmStates;
-  std::vector<int64_t> off_copy;
-  if ((st = host_offsets(nseq, offsets_host, offsets_dev, off_copy, stream)) != CV_OK) return st;
-  if ((st = ensure_post_tables(h)) != CV_OK) return st;
-  const int np = h->pnp;
-  h->last_launches = 0;
-  h->last_kernel = generic ? CV_KERNEL_GENERIC : CV_KERNEL_AUTO;
-  h->last_np = np;
-  h->last_mt = generic ? -1 : cvp::kPostGroup;
-  if (nseq == 0 && cnt) {  // overwritten, not accumulated: an empty batch counts nothing
-    HIP_TRY(hipMemsetAsync(cnt->pi_cnt, 0, (size_t)h->N * 8, stream));
-    HIP_TRY(hipMemsetAsync(cnt->a_cnt, 0, (size_t)h->N * h->N * 8, stream));
-    if (cnt->b_cnt) HIP_TRY(hipMemsetAsync(cnt->b_cnt, 0, (size_t)h->N * (size_t)h->V * 8, stream));
-  }
-  if (nseq == 0) return CV_OK;
-  if (h->ws_rec) HIP_TRY(hipStreamWaitEvent(stream, h->ws_done, 0));
-
-  const bool store = path_dev || gamma_dev || smp || cnt;
-  const bool bc = cnt && cnt->b_cnt;
-  if (bc && (emis || !cnt->grad || !obs_dev || gamma_dev || (cnt->egrad && cnt->ld_grad != h->N)))
-    return set_err(CV_EINTERNAL, "emission counts: the discrete model under the gradient arm only");
-  if (bc && h->V > INT32_MAX) return set_err(CV_ELIMIT, "emission counts cover V <= %d (V=%lld)", INT32_MAX, (long long)h->V);
-  const bool bc_ws = bc && !cnt->egrad;  // the rows w_s gamma go to the workspace
-  const uint64_t row_bytes = (uint64_t)np * 8;
-  // counts: the U row and inv of every element beside its forward row
-  const uint64_t per_elem =
-      (store ? row_bytes : 0) + (cnt ? row_bytes + 8 : 0) + (emis ? row_bytes + 4 : 0) + (bc_ws ? row_bytes : 0);
-  // ... and the GEMM's partial tiles, under the same cap: at most cvp::kXiPartCap, and half of a
-  // cap that is smaller than twice that
-  uint64_t part_cap = 0;
-  std::vector<cvplan::Chunk> chunks;
-  uint64_t max_elems = 0;
-  if (per_elem == 0) {
-    chunks.emplace_back(0, nseq);
-  } else {
-    // 2 KiB of rows per element at N = 256: the f64 trellis's default cap (HBM3E: 288 GB per GPU)
-    uint64_t cap = o.workspace_bytes ? o.workspace_bytes : default_workspace_cap(h->ps_rows.bytes, kDefaultWorkspaceT64);
-    if (cnt) {
-      const uint64_t most = std::min<uint64_t>(cvp::kXiPartCap, (uint64_t)cvp::kXiMaxParts * np * row_bytes);
-      part_cap = cap >= 2 * most ? most : cap / 2;
-      cap -= part_cap;
-    }
-    uint64_t elem_cap = cap / per_elem;
-    if (emis) {  // the staged rows of a sequence cannot be split, and a chunk is indexed by int32
-      elem_cap = std::min<uint64_t>(elem_cap, INT32_MAX);
-      for (int64_t s = 0; s < nseq; ++s) {
-        const uint64_t T = (uint64_t)(offsets_host[s + 1] - offsets_host[s]);
-        if (T > INT32_MAX) return set_err(CV_ELIMIT, "sequence %lld: %llu elements of dense emissions", (long long)s, (unsigned long long)T);
-        if (T > elem_cap)
-          return set_err(CV_ENOMEM, "sequence %lld needs %llu bytes of staged emissions and rows (T=%llu, NP=%d), workspace cap %llu",
-                         (long long)s, (unsigned long long)(T * per_elem), (unsigned long long)T, np, (unsigned long long)cap);
-      }
-    }
-    max_elems = std::max<uint64_t>(cvplan::split_equal_shares(offsets_host, nseq, elem_cap, chunks).max_elems, 1);
-    if ((st = h->ps_rows.ensure((size_t)(max_elems * per_elem))) != CV_OK) return st;
-  }
-  // the workspace: [max_elems][NP] forward rows (store), [max_elems][NP] U rows (counts),
-  // [max_elems][NP] staged emission rows (emis), [max_elems][NP] rows w_s gamma (emission counts
-  // without the caller's gamma), [max_elems] inv (counts), [max_elems] int32 observation indices
-  // (emis); NP * 8 is a multiple of 512
-  double* ws_next = h->ps_rows.as<double>();
-  auto take_rows = [&](bool on, uint64_t width) {
-    double* const p = on ? ws_next : nullptr;
-    if (on) ws_next += max_elems * width;
-    return p;
-  };
-  double* const ws_rows = take_rows(store, (uint64_t)np);
-  double* const ws_urows = take_rows(cnt != nullptr, (uint64_t)np);
-  double* const ws_emis = take_rows(emis != nullptr, (uint64_t)np);
-  double* const ws_g = take_rows(bc_ws, (uint64_t)np);
-  double* const ws_inv = take_rows(cnt != nullptr, 1);
-  int32_t* const ws_idx = emis ? reinterpret_cast<int32_t*>(ws_next) : nullptr;
-  const int64_t xi_key = cvk::tuning().xi_part_rows;
-  if (cnt) {
-    int64_t most_parts = 1;
-    for (const auto& c : chunks) {
-      const int64_t rows = offsets_host[c.second] - offsets_host[c.first];
-      const int64_t per = cvp::post_xi_part_rows(rows, np, xi_key, part_cap);
-      most_parts = std::max(most_parts, (rows + per - 1) / per);
-    }
-    if ((st = h->ps_xi_part.ensure((size_t)most_parts * np * row_bytes)) != CV_OK) return st;
-    if ((st = h->ps_xi_s.ensure((size_t)np * row_bytes)) != CV_OK) return st;
-    if ((st = h->ps_g0.ensure((size_t)nseq * row_bytes)) != CV_OK) return st;
-    HIP_TRY(hipMemsetAsync(h->ps_xi_s.p, 0, (size_t)np * row_bytes, stream));
-  }
-  // emission counts: the sort's scratch and the run sums of the largest chunk, the accumulator
-  const int64_t bc_key = cvk::tuning().bcnt_part_rows;
-  cvb::BcntArgs bq{};
-  if (bc) {
-    if (max_elems > INT32_MAX) return set_err(CV_ELIMIT, "emission counts: a chunk of %llu elements", (unsigned long long)max_elems);
-    int64_t most_runs = 1;
-    for (const auto& c : chunks) {
-      const int64_t rows = offsets_host[c.second] - offsets_host[c.first];
-      most_runs = std::max(most_runs, cvb::bcnt_max_runs(rows, cvb::bcnt_part_rows(rows, np, bc_key), h->V));
-    }
-    size_t tmp = 0;
-    hipError_t qe = cvb::bcnt_sort_tmp_bytes((int64_t)max_elems, h->V, &tmp);
-    if (qe != hipSuccess) return set_err(CV_EDEVICE, "emission-count sort sizing failed: %s", hipGetErrorString(qe));
-    auto up = [](size_t n) { return (n + 255) / 256 * 256; };
-    const size_t plane = up((size_t)max_elems * 4), tmp_b = up(tmp), keys_b = up((size_t)most_runs * 4);
-    if ((st = h->ps_bc_sort.ensure(5 * plane + tmp_b + keys_b)) != CV_OK) return st;
-    if ((st = h->ps_bc_part.ensure((size_t)most_runs * row_bytes)) != CV_OK) return st;
-    if ((st = h->ps_bc_acc.ensure((size_t)h->V * row_bytes)) != CV_OK) return st;
-    HIP_TRY(hipMemsetAsync(h->ps_bc_acc.p, 0, (size_t)h->V * row_bytes, stream));
-    char* const sp = h->ps_bc_sort.as<char>();
-    bq.key_in = reinterpret_cast<uint32_t*>(sp);
-    bq.key_out = reinterpret_cast<uint32_t*>(sp + plane);
-    bq.row_in = reinterpret_cast<int32_t*>(sp + 2 * plane);
-    bq.row_out = reinterpret_cast<int32_t*>(sp + 3 * plane);
-    bq.run = reinterpret_cast<int32_t*>(sp + 4 * plane);
-    bq.sort_tmp = sp + 5 * plane;
-    bq.sort_tmp_bytes = tmp_b;
-    bq.run_key = reinterpret_cast<uint32_t*>(sp + 5 * plane + tmp_b);
-    bq.max_runs = most_runs;
-    bq.part = h->ps_bc_part.as<double>();
-    bq.acc = h->ps_bc_acc.as<double>();
-    bq.offsets = offsets_dev;
-    bq.obs = obs_dev;
-    bq.status = status_dev;
-    bq.nobs = h->V;
-    bq.nstates = h->N;
-    bq.np = np;
-  }
-  if (emis) {
-    if ((st = h->ps_kshift.ensure((size_t)nseq * 8)) != CV_OK) return st;
-    HIP_TRY(hipMemsetAsync(h->ps_kshift.p, 0, (size_t)nseq * 8, stream));
-  }
-  // longest first inside each chunk (stable), so a group's sequences have similar lengths
-  const int32_t* order_dev = nullptr;
-  if (cvplan::varlen(offsets_host, nseq)) {
-    if (nseq > INT32_MAX) return set_err(CV_EINVAL, "too many sequences (%lld)", (long long)nseq);
-    h->order_host.resize((size_t)nseq);
-    cvplan::longest_first(offsets_host, chunks, h->order_host.data(), nullptr, h->sort_pos);
-    if ((st = upload_order(h->ps_order, h->ps_pin, h->order_host.data(), nseq, stream, &order_dev)) != CV_OK) return st;
-  }
-  const size_t nev = 4 * chunks.size();
-  size_t eb;
-  if ((st = reserve_events(h, false, nev, &eb)) != CV_OK) return st;
-  // scoring mode: no backward launch, and cv_last_timing says so exactly (bt_ms = 0)
-  if (!store) std::fill(h->ev_nobt.begin() + (ptrdiff_t)(eb / 4), h->ev_nobt.begin() + (ptrdiff_t)(eb / 4 + chunks.size()), (uint8_t)1);
-  for (size_t ci = 0; ci < chunks.size(); ++ci) {
-    const auto& c = chunks[ci];
-    cvp::PostArgs g{};
-    g.pi = h->p_pi.as<double>();
-    g.a = h->p_a.as<double>();
-    g.at = h->p_at.as<double>();
-    g.et = h->p_et.as<double>();
-    g.offsets = offsets_dev;
-    g.obs = obs_dev;
-    g.forced = o.forced;
-    g.order = order_dev;
-    g.seq_begin = c.first;
-    g.seq_end = c.second;
-    g.elem_base = offsets_host[c.first];
-    g.nstates = h->N;
-    g.np = np;
-    g.nobs = h->V;
-    g.rows = ws_rows;
-    g.loglik = loglik_dev;
-    g.status = status_dev;
-    g.path = path_dev;
-    g.gamma = gamma_dev;
-    g.dump = h->p_dump.as<double>();
-    if (cnt) {
-      g.urows = ws_urows;
-      g.inv = ws_inv;
-      g.g0 = h->ps_g0.as<double>();
-      g.weight = cnt->weight;
-      g.egrad = cnt->egrad;
-      g.ld_grad = cnt->ld_grad;
-      if (bc_ws) {  // the kernels index egrad by absolute element: (ws_g - e0 NP)[e NP] = ws_g[(e - e0) NP]
-        g.egrad = reinterpret_cast<double*>(reinterpret_cast<uintptr_t>(ws_g) - (uintptr_t)g.elem_base * row_bytes);
-        g.ld_grad = np;
-      }
-    }
-    hipEvent_t f0 = h->ev[eb + 4 * ci], f1 = h->ev[eb + 4 * ci + 1], b0 = h->ev[eb + 4 * ci + 2], b1 = h->ev[eb + 4 * ci + 3];
-    HIP_TRY(hipEventRecord(f0, stream));
-    hipError_t err;
-    if (emis) {
-      const int64_t e0 = offsets_host[c.first], e1 = offsets_host[c.second];
-      cvem::EmisLinArgs eg{};
-      eg.src = emis->p;
-      eg.ld = emis->ld;
-      eg.e0 = e0;
-      eg.nrows = e1 - e0;
-      eg.nstates = h->N;
-      eg.stride = np;
-      eg.dst = ws_emis;
-      eg.idx = ws_idx;
-      eg.offsets = offsets_dev;
-      eg.seq_begin = c.first;
-      eg.seq_end = c.second;
-      eg.kshift = h->ps_kshift.as<int64_t>();
-      err = cvem::launch_emis_prepare_lin(eg, h->cus, stream);
-      if (err != hipSuccess) return set_err(CV_EDEVICE, "emission staging launch failed: %s", hipGetErrorString(err));
-      g.et = ws_emis;
-      // the kernels index obs by absolute element: (idx - e0)[e] = idx[e - e0]
-      g.obs = reinterpret_cast<const int32_t*>(reinterpret_cast<uintptr_t>(ws_idx) - (uintptr_t)e0 * 4);
-      g.nobs = e1 - e0;
-      g.kshift = h->ps_kshift.as<int64_t>();
-    }
-    err = cvp::launch_post_fwd(g, generic, stream);
-    if (err != hipSuccess) return set_err(CV_EDEVICE, "posterior forward launch failed: %s", hipGetErrorString(err));
-    HIP_TRY(hipEventRecord(f1, stream));
-    HIP_TRY(hipEventRecord(b0, stream));
-    if (smp) {
-      cvs::SampleArgs sg{};
-      sg.at = g.at;
-      sg.rows = g.rows;
-      sg.offsets = offsets_dev;
-      sg.order = order_dev;
-      sg.seq_begin = c.first;
-      sg.seq_end = c.second;
-      sg.elem_base = g.elem_base;
-      sg.nstates = h->N;
-      sg.np = np;
-      sg.status = status_dev;
-      sg.path = smp->path;
-      sg.plane = offsets_host[nseq];
-      sg.draws = smp->draws;
-      sg.seed = smp->seed;
-      sg.seq_base = smp->seq_base;
-      err = cvs::launch_sample(sg, generic, stream);
-      if (err == hipSuccess && smp->score) {
-        cvs::SampleScoreArgs ss{};
-        ss.path = smp->path;
-        ss.plane = sg.plane;
-        ss.draws = smp->draws;
-        ss.obs = obs_dev;
-        ss.offsets = offsets_dev;
-        ss.order = order_dev;
-        ss.seq_begin = c.first;
-        ss.seq_end = c.second;
-        ss.nseq = nseq;
-        ss.nstates = h->N;
-        ss.pi64 = h->d_pi64.as<double>();
-        ss.a64 = h->d_a64.as<double>();
-        ss.et64 = h->d_et64.as<double>();
-        ss.status = status_dev;
-        ss.score = smp->score;
-        err = cvs::launch_sample_score(ss, stream);
-      }
-      if (err != hipSuccess) return set_err(CV_EDEVICE, "sampling launch failed: %s", hipGetErrorString(err));
-    } else if (store) {
-      err = cnt && cnt->grad ? cvp::launch_post_grad_bwd(g, generic, stream) : cvp::launch_post_bwd(g, generic, stream);
-      if (err != hipSuccess) return set_err(CV_EDEVICE, "posterior backward launch failed: %s", hipGetErrorString(err));
-    }
-    if (cnt) {
-      cvp::XiArgs x{};
-      x.rows = ws_rows;
-      x.urows = ws_urows;
-      x.inv = ws_inv;
-      x.nrows = offsets_host[c.second] - offsets_host[c.first];
-      x.part_rows = cvp::post_xi_part_rows(x.nrows, np, xi_key, part_cap);
-      x.nparts = (x.nrows + x.part_rows - 1) / x.part_rows;
-      x.np = np;
-      x.part = h->ps_xi_part.as<double>();
-      x.s = h->ps_xi_s.as<double>();
-      err = cvp::launch_post_xi(x, stream);
-      if (err == hipSuccess && ci + 1 == chunks.size()) {
-        cvp::CountsFinalArgs f{};
-        f.s = x.s;
-        f.a = g.a;
-        f.g0 = g.g0;
-        f.status = status_dev;
-        f.nseq = nseq;
-        f.nstates = h->N;
-        f.np = np;
-        f.a_cnt = cnt->a_cnt;
-        f.pi_cnt = cnt->pi_cnt;
-        err = cvp::launch_post_counts_final(f, stream);
-      }
-      if (err == hipSuccess && bc) {
-        cvb::BcntArgs b = bq;
-        b.seq_begin = c.first;
-        b.seq_end = c.second;
-        b.elem_base = g.elem_base;
-        b.nrows = x.nrows;
-        b.ld = g.ld_grad;
-        b.g = bc_ws ? ws_g : cnt->egrad + (size_t)g.elem_base * (size_t)h->N;
-        b.part_rows = cvb::bcnt_part_rows(b.nrows, np, bc_key);
-        err = cvb::launch_bcnt_chunk(b, stream);
-        if (err == hipSuccess && ci + 1 == chunks.size())
-          err = cvb::launch_bcnt_final(bq.acc, h->V, h->N, np, cnt->b_cnt, stream);
-      }
-      if (err != hipSuccess) return set_err(CV_EDEVICE, "expected-counts launch failed: %s", hipGetErrorString(err));
-    }
-    HIP_TRY(hipEventRecord(b1, stream));
-    h->last_launches = (int64_t)ci + 1;
-  }
-  return end_call(h, false, nev, stream);
-}
-
-// Core of cv_sample_batch*: forward filtering, backward sampling.  posterior_device's plan with the
-// sampler in place of the backward pass; all pointers are device pointers except offsets_host.
-cv_status sample_draws_ok(int32_t draws) {
-  if (draws < 1 || draws > cvs::kSampleMaxDraws)
-    return set_err(CV_EINVAL, "draws = %d outside [1, %d]", draws, cvs::kSampleMaxDraws);
-  return CV_OK;
-}
-cv_status sample_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, const int64_t* offsets_dev,
-                        const int32_t* obs_dev, int32_t draws, uint64_t seed, int64_t seq_base, const cv_opts& o,
-                        int32_t* path_dev, double* score_dev, double* loglik_dev, uint8_t* status_dev,
-                        hipStream_t stream) {
-  cv_status st = sample_draws_ok(draws);
-  if (st != CV_OK) return st;
-  const SampleReq smp{draws, seed, seq_base, path_dev, score_dev};
-  return posterior_device(h, nseq, offsets_host, offsets_dev, obs_dev, o, loglik_dev, nullptr, nullptr, status_dev, stream,
-                          nullptr, &smp);
-}
-
 // ---- K-best (list) Viterbi: cv_kbest_batch* ---------------------------------------------------
 // Core of cv_kbest_batch*: all pointers are device pointers except offsets_host.  Chunks of whole
 // sequences (original order) whose u16 back-pointers (N * KT * 2 bytes per element) fit the
@@ -1939,96 +1178,13 @@ cv_status kbest_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, con
   return end_call(h, false, nev, stream);
 }
 
-cv_opts default_opts() {
+}  // namespace
+
+cv_opts cvi::default_opts() {
   cv_opts o;
   cv_opts_init(&o);
   return o;
 }
-
-// One host-pointer batch call (cv_decode_batch, cv_posterior_batch, cv_kbest_batch,
-// cv_decode_emissions, cv_posterior_emissions) through the handle's staging buffers; the caller
-// holds h->mu and has selected the device.  stage() checks the caller's arrays and only then enqueues the copies from
-// them; the entry runs its core on the st_* buffers and fetches the results.  obs / path / forced
-// are indexed by absolute element offset: the element slice is [base, total).
-struct HostBatch {
-  cv_hmm* h;
-  int64_t nseq;
-  const int64_t* offsets;
-  const int32_t* obs;  // null: this call stages no observations
-  hipStream_t stream;
-  int64_t base = 0, total = 0;
-  hipError_t err = hipSuccess;  // of the result copies (finish)
-
-  size_t plane() const { return (size_t)std::max<int64_t>(total, 1); }
-
-  // Sizes st_path (`planes` element planes), st_score (`width` per sequence) and st_status too.
-  // check_obs: the host range check (decode only; posterior and K-best report CV_SEQ_BADOBS from
-  // the device).  forced_host: o.forced is the caller's host array -> checked, staged and
-  // rewritten to the device copy (false: it is a validated device array already).
-  cv_status stage(cv_opts& o, size_t planes, size_t width, bool check_obs = false, bool forced_host = true) {
-    cv_status st = check_batch(nseq, offsets);
-    if (st != CV_OK) return st;
-    base = offsets[0], total = offsets[nseq];
-    const int32_t* ob = check_obs ? obs : nullptr;
-    const int32_t* fr = forced_host ? o.forced : nullptr;
-    const int64_t V = h->V, N = h->N;
-    int64_t k;
-    if (ob && (k = first_bad(base, total, [&](int64_t i) { return ob[i] < 0 || ob[i] >= V; })) >= 0)
-      return set_err(CV_EINVAL, "obs[%lld] = %d out of range [0,%lld)", (long long)k, ob[k], (long long)V);
-    if (fr && (k = first_bad(base, total, [&](int64_t i) { return fr[i] < -1 || fr[i] >= N; })) >= 0)
-      return set_err(CV_EINVAL, "forced[%lld] = %d out of range [-1,%d)", (long long)k, fr[k], h->N);
-    if ((st = h->st_off.ensure((size_t)(nseq + 1) * 8)) != CV_OK) return st;
-    if (obs && (st = h->st_obs.ensure(plane() * 4)) != CV_OK) return st;
-    if (planes && (st = h->st_path.ensure(plane() * planes * 4)) != CV_OK) return st;
-    if ((st = h->st_score.ensure((size_t)nseq * width * 8)) != CV_OK) return st;
-    if ((st = h->st_status.ensure((size_t)nseq)) != CV_OK) return st;
-    if (fr && (st = h->st_forced.ensure(plane() * 4)) != CV_OK) return st;
-    HIP_TRY(hipMemcpyAsync(h->st_off.p, offsets, (size_t)(nseq + 1) * 8, hipMemcpyHostToDevice, stream));
-    const size_t n = (size_t)(total - base) * 4;
-    if (obs && n) HIP_TRY(hipMemcpyAsync(h->st_obs.as<int32_t>() + base, obs + base, n, hipMemcpyHostToDevice, stream));
-    if (fr && n) HIP_TRY(hipMemcpyAsync(h->st_forced.as<int32_t>() + base, fr + base, n, hipMemcpyHostToDevice, stream));
-    if (fr) o.forced = h->st_forced.as<int32_t>();
-    return CV_OK;
-  }
-  // After stage(): the caller's dense emission rows (cv_decode_emissions, cv_posterior_emissions),
-  // the N scores of each row compact on the device (the columns beyond N are never read).
-  cv_status stage_emis(const double* emis, int64_t ld, EmisSrc* src) {
-    const int64_t N = h->N, rows = total - base;
-    cv_status st = h->st_emis.ensure((size_t)std::max<int64_t>(rows, 1) * N * 8);
-    if (st != CV_OK) return st;
-    if (rows > 0)
-      HIP_TRY(hipMemcpy2DAsync(h->st_emis.p, (size_t)N * 8, emis + base * ld, (size_t)ld * 8, (size_t)N * 8,
-                               (size_t)rows, hipMemcpyHostToDevice, stream));
-    // row e of the staging at p + e * N: the staging holds the elements from `base` on
-    *src = EmisSrc{reinterpret_cast<const double*>(reinterpret_cast<uintptr_t>(h->st_emis.p) -
-                                                   (uintptr_t)base * (uintptr_t)N * 8),
-                   N};
-    return CV_OK;
-  }
-  // a failed core's work is waited for before the caller sees its status
-  cv_status fail(cv_status st) const {
-    (void)hipStreamSynchronize(stream);
-    return st;
-  }
-  // the element slice of plane r of buf (`width` T per element) -> the same slice of out
-  template <typename T>
-  void fetch_elems(T* out, const DevBuf& buf, size_t width = 1, size_t r = 0) {
-    const size_t at = (r * (size_t)total + (size_t)base) * width, n = (size_t)(total - base) * width * sizeof(T);
-    if (err == hipSuccess && n) err = hipMemcpyAsync(out + at, buf.as<T>() + at, n, hipMemcpyDeviceToHost, stream);
-  }
-  // nseq items of `width` T
-  template <typename T>
-  void fetch_seqs(T* out, const DevBuf& buf, size_t width = 1) {
-    if (err == hipSuccess) err = hipMemcpyAsync(out, buf.p, (size_t)nseq * width * sizeof(T), hipMemcpyDeviceToHost, stream);
-  }
-  // the results are in the caller's arrays
-  cv_status finish() {
-    if (err == hipSuccess) err = hipStreamSynchronize(stream);
-    return err == hipSuccess ? CV_OK : set_err(CV_EDEVICE, "copying the results back failed: %s", hipGetErrorString(err));
-  }
-};
-
-}  // namespace
 
 // ===================================================================================
 extern "C" {
@@ -2127,8 +1283,9 @@ CV_API cv_status cv_hmm_release_workspaces(cv_hmm* h) {
                     &h->chainb.q, &h->chainb.ends, &h->chainb.gid, &h->chainb.gpath, &h->chainb.first,
                     &h->chainb.rpsi, &h->chainb.rows, &h->chainb.small, &h->chainb.rpath, &h->chainb.soff,
                     &h->chainb.sobs, &h->chainb.spath, &h->chainb.sres, &h->chainb.sinit, &h->chainb.slast,
-                    &h->chainb.spsi, &h->ps_rows,
-                    &h->ps_order, &h->ps_kshift, &h->st_gamma, &h->ps_xi_part, &h->ps_xi_s, &h->ps_g0, &h->st_cnt, &h->ps_bc_acc, &h->ps_bc_sort, &h->ps_bc_part, &h->kb_bp, &h->kb_last, &h->kb_order, &h->kb_end, &h->st_count,
+                    &h->chainb.spsi, &h->ps_rows, &h->ps_order, &h->ps_kshift, &h->st_gamma, &h->ps_xi_part,
+                    &h->ps_xi_s, &h->ps_g0, &h->st_cnt, &h->ps_bc_acc, &h->ps_bc_sort, &h->ps_bc_part, &h->kb_bp,
+                    &h->kb_last, &h->kb_order, &h->kb_end, &h->st_count,
                     &h->st_emis, &h->fx_cert, &h->fx_idx, &h->fx_obs2, &h->fx_path2, &h->fx_score2, &h->fx_status2,
                     &h->ru_mu, &h->ru_r, &h->ru_e})
     b->release();
@@ -2702,118 +1859,6 @@ CV_API cv_status cv_decode_batch(cv_hmm* h, int64_t nseq, const int64_t* offsets
                             false, false, true);
 }
 
-CV_API cv_status cv_posterior_batch_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
-                                           const int64_t* offsets_dev, const int32_t* obs_dev, const cv_opts* opts,
-                                           double* loglik_dev, int32_t* path_dev, double* gamma_dev,
-                                           uint8_t* status_dev) {
-  if (!h) return set_err(CV_EINVAL, "null handle");
-  if (nseq < 0) return set_err(CV_EINVAL, "nseq < 0");
-  if (nseq > 0 && (!offsets_dev || !obs_dev || !loglik_dev || !status_dev))
-    return set_err(CV_EINVAL, "null device buffer");
-  CV_LOCK(h);
-  cv_status st = set_device(h);
-  if (st != CV_OK) return st;
-  const cv_opts o = opts ? *opts : default_opts();
-  hipStream_t stream = o.stream ? (hipStream_t)o.stream : h->stream;
-  return posterior_device(h, nseq, offsets_host, offsets_dev, obs_dev, o, loglik_dev, path_dev, gamma_dev, status_dev,
-                          stream);
-}
-
-CV_API cv_status cv_posterior_batch(cv_hmm* h, int64_t nseq, const int64_t* offsets, const int32_t* obs,
-                                    const cv_opts* opts, double* loglik_out, int32_t* path_out, double* gamma_out,
-                                    uint8_t* status_out) {
-  if (!h) return set_err(CV_EINVAL, "null handle");
-  if (nseq < 0 || (nseq > 0 && (!offsets || !obs || !loglik_out || !status_out)))
-    return set_err(CV_EINVAL, "null argument");
-  CV_LOCK(h);
-  cv_status st = set_device(h);
-  if (st != CV_OK) return st;
-  cv_opts o = opts ? *opts : default_opts();
-  if (nseq == 0) return CV_OK;
-  const size_t N = (size_t)h->N;
-  // the observations are range-checked on the device (CV_SEQ_BADOBS), as in the _device variant
-  HostBatch hb{h, nseq, offsets, obs, o.stream ? (hipStream_t)o.stream : h->stream};
-  if ((st = hb.stage(o, path_out ? 1 : 0, 1)) != CV_OK) return st;
-  if (gamma_out && (st = h->st_gamma.ensure(hb.plane() * N * 8)) != CV_OK) return st;
-  st = posterior_device(h, nseq, offsets, h->st_off.as<int64_t>(), h->st_obs.as<int32_t>(), o, h->st_score.as<double>(),
-                        path_out ? h->st_path.as<int32_t>() : nullptr, gamma_out ? h->st_gamma.as<double>() : nullptr,
-                        h->st_status.as<uint8_t>(), hb.stream);
-  if (st != CV_OK) return hb.fail(st);
-  if (path_out) hb.fetch_elems(path_out, h->st_path);
-  if (gamma_out) hb.fetch_elems(gamma_out, h->st_gamma, N);
-  hb.fetch_seqs(loglik_out, h->st_score);
-  hb.fetch_seqs(status_out, h->st_status);
-  if ((st = hb.finish()) != CV_OK) return st;
-  for (int64_t s = 0; s < nseq; ++s)
-    if (status_out[s] == CV_SEQ_INFEASIBLE)
-      return set_err(CV_EINFEASIBLE, "sequence %lld has likelihood 0", (long long)s);
-  return CV_OK;
-}
-
-// ---- posterior path sampling: cv_sample_batch* -------------------------------------------------
-CV_API cv_status cv_sample_batch_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
-                                        const int64_t* offsets_dev, const int32_t* obs_dev, int32_t draws,
-                                        uint64_t seed, int64_t seq_base, const cv_opts* opts, int32_t* path_dev,
-                                        double* score_dev, double* loglik_dev, uint8_t* status_dev) {
-  if (!h) return set_err(CV_EINVAL, "null handle");
-  if (nseq < 0) return set_err(CV_EINVAL, "nseq < 0");
-  cv_status st = sample_draws_ok(draws);
-  if (st != CV_OK) return st;
-  if (nseq > 0 && (!offsets_dev || !obs_dev || !path_dev || !status_dev)) return set_err(CV_EINVAL, "null device buffer");
-  CV_LOCK(h);
-  if ((st = set_device(h)) != CV_OK) return st;
-  const cv_opts o = opts ? *opts : default_opts();
-  hipStream_t stream = o.stream ? (hipStream_t)o.stream : h->stream;
-  double* ll = loglik_dev;
-  if (!ll && nseq > 0) {  // the forward pass always writes the log-likelihoods: to the staging when nobody asks
-    if ((st = h->st_score.ensure((size_t)nseq * 8)) != CV_OK) return st;
-    ll = h->st_score.as<double>();
-  }
-  return sample_device(h, nseq, offsets_host, offsets_dev, obs_dev, draws, seed, seq_base, o, path_dev, score_dev, ll,
-                       status_dev, stream);
-}
-
-CV_API cv_status cv_sample_batch(cv_hmm* h, int64_t nseq, const int64_t* offsets, const int32_t* obs, int32_t draws,
-                                 uint64_t seed, int64_t seq_base, const cv_opts* opts, int32_t* path_out,
-                                 double* score_out, double* loglik_out, uint8_t* status_out) {
-  if (!h) return set_err(CV_EINVAL, "null handle");
-  cv_status st = sample_draws_ok(draws);
-  if (st != CV_OK) return st;
-  if (nseq < 0 || (nseq > 0 && (!offsets || !obs || !path_out || !status_out))) return set_err(CV_EINVAL, "null argument");
-  CV_LOCK(h);
-  if ((st = set_device(h)) != CV_OK) return st;
-  cv_opts o = opts ? *opts : default_opts();
-  if (nseq == 0) return CV_OK;
-  const size_t R = (size_t)draws, B = (size_t)nseq;
-  // the observations are range-checked on the device (CV_SEQ_BADOBS), as in the _device variant
-  HostBatch hb{h, nseq, offsets, obs, o.stream ? (hipStream_t)o.stream : h->stream};
-  // st_score: [nseq] log-likelihoods, then the [R][nseq] score planes
-  if ((st = hb.stage(o, R, R + 1)) != CV_OK) return st;
-  double* const ll_dev = h->st_score.as<double>();
-  double* const sc_dev = score_out ? ll_dev + B : nullptr;
-  st = sample_device(h, nseq, offsets, h->st_off.as<int64_t>(), h->st_obs.as<int32_t>(), draws, seed, seq_base, o,
-                     h->st_path.as<int32_t>(), sc_dev, ll_dev, h->st_status.as<uint8_t>(), hb.stream);
-  if (st != CV_OK) return hb.fail(st);
-  for (size_t r = 0; r < R; ++r)  // plane r of the staging and of path_out: offsets[nseq] elements each
-    hb.fetch_elems(path_out, h->st_path, 1, r);
-  // the scores come back through pinned staging: an empty sequence's slots of score_out stay untouched
-  const size_t nsc = (score_out ? R * B : 0) + B;
-  if (!h->sm_pin.ensure(nsc * 8)) return hb.fail(set_err(CV_ENOMEM, "pinned staging of %zu scores failed", nsc));
-  double* const pin = h->sm_pin.as<double>();
-  if (hb.err == hipSuccess) hb.err = hipMemcpyAsync(pin, ll_dev, nsc * 8, hipMemcpyDeviceToHost, hb.stream);
-  hb.fetch_seqs(status_out, h->st_status);
-  if ((st = hb.finish()) != CV_OK) return st;
-  if (loglik_out) std::memcpy(loglik_out, pin, B * 8);
-  int64_t infeasible = -1;
-  for (int64_t s = 0; s < nseq; ++s) {
-    if (status_out[s] == CV_SEQ_INFEASIBLE && infeasible < 0) infeasible = s;
-    if (score_out && status_out[s] != CV_SEQ_EMPTY)
-      for (size_t r = 0; r < R; ++r) score_out[r * B + (size_t)s] = pin[B + r * B + (size_t)s];
-  }
-  if (infeasible >= 0) return set_err(CV_EINFEASIBLE, "sequence %lld has likelihood 0", (long long)infeasible);
-  return CV_OK;
-}
-
 CV_API cv_status cv_kbest_batch_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
                                        const int64_t* offsets_dev, const int32_t* obs_dev, int32_t k,
                                        const cv_opts* opts, int32_t* path_dev, double* score_dev,
@@ -2857,10 +1902,7 @@ CV_API cv_status cv_kbest_batch(cv_hmm* h, int64_t nseq, const int64_t* offsets,
   hb.fetch_seqs(count_out, h->st_count);
   hb.fetch_seqs(status_out, h->st_status);
   if ((st = hb.finish()) != CV_OK) return st;
-  for (int64_t s = 0; s < nseq; ++s)
-    if (status_out[s] == CV_SEQ_INFEASIBLE)
-      return set_err(CV_EINFEASIBLE, "sequence %lld has no path of finite score", (long long)s);
-  return CV_OK;
+  return report_infeasible(nseq, status_out, "has no path of finite score");
 }
 
 // ---- decode of caller-supplied emission scores: cv_decode_emissions* -------------------------
@@ -2918,324 +1960,6 @@ CV_API cv_status cv_decode_emissions(cv_hmm* h, int64_t nseq, const int64_t* off
   hb.fetch_seqs(score_out, h->st_score);
   hb.fetch_seqs(status_out, h->st_status);
   return hb.finish();
-}
-
-// ---- evaluation under caller-supplied emission scores: cv_posterior_emissions* ----------------
-// The checks that need no device, made before any copy from the caller's arrays.
-static cv_status posterior_emissions_args_ok(const cv_hmm* h, int64_t ld, const cv_opts& o) {
-  if (ld < h->N) return set_err(CV_EINVAL, "ld = %lld is less than N = %d", (long long)ld, h->N);
-  return posterior_opts_ok(h, o);
-}
-
-CV_API cv_status cv_posterior_emissions_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
-                                               const int64_t* offsets_dev, const double* emis_dev, int64_t ld,
-                                               const cv_opts* opts, double* loglik_dev, int32_t* path_dev,
-                                               double* gamma_dev, uint8_t* status_dev) {
-  if (!h) return set_err(CV_EINVAL, "null handle");
-  if (nseq < 0) return set_err(CV_EINVAL, "nseq < 0");
-  if (nseq > 0 && (!offsets_dev || !emis_dev || !loglik_dev || !status_dev))
-    return set_err(CV_EINVAL, "null device buffer");
-  const cv_opts o = opts ? *opts : default_opts();
-  cv_status st = posterior_emissions_args_ok(h, ld, o);
-  if (st != CV_OK) return st;
-  CV_LOCK(h);
-  if ((st = set_device(h)) != CV_OK) return st;
-  hipStream_t stream = o.stream ? (hipStream_t)o.stream : h->stream;
-  const EmisSrc src{emis_dev, ld};
-  return posterior_device(h, nseq, offsets_host, offsets_dev, nullptr, o, loglik_dev, path_dev, gamma_dev, status_dev,
-                          stream, &src);
-}
-
-CV_API cv_status cv_posterior_emissions(cv_hmm* h, int64_t nseq, const int64_t* offsets, const double* emis,
-                                        int64_t ld, const cv_opts* opts, double* loglik_out, int32_t* path_out,
-                                        double* gamma_out, uint8_t* status_out) {
-  if (!h) return set_err(CV_EINVAL, "null handle");
-  if (nseq < 0 || (nseq > 0 && (!offsets || !emis || !loglik_out || !status_out)))
-    return set_err(CV_EINVAL, "null argument");
-  cv_opts o = opts ? *opts : default_opts();
-  cv_status st = posterior_emissions_args_ok(h, ld, o);
-  if (st != CV_OK) return st;
-  CV_LOCK(h);
-  if ((st = set_device(h)) != CV_OK) return st;
-  if (nseq == 0) return CV_OK;
-  const int64_t N = h->N;
-  HostBatch hb{h, nseq, offsets, nullptr, o.stream ? (hipStream_t)o.stream : h->stream};
-  if ((st = hb.stage(o, path_out ? 1 : 0, 1)) != CV_OK) return st;
-  if (gamma_out && (st = h->st_gamma.ensure(hb.plane() * (size_t)N * 8)) != CV_OK) return st;
-  EmisSrc src;
-  if ((st = hb.stage_emis(emis, ld, &src)) != CV_OK) return st;
-  st = posterior_device(h, nseq, offsets, h->st_off.as<int64_t>(), nullptr, o, h->st_score.as<double>(),
-                        path_out ? h->st_path.as<int32_t>() : nullptr, gamma_out ? h->st_gamma.as<double>() : nullptr,
-                        h->st_status.as<uint8_t>(), hb.stream, &src);
-  if (st != CV_OK) return hb.fail(st);
-  if (path_out) hb.fetch_elems(path_out, h->st_path);
-  if (gamma_out) hb.fetch_elems(gamma_out, h->st_gamma, (size_t)N);
-  hb.fetch_seqs(loglik_out, h->st_score);
-  hb.fetch_seqs(status_out, h->st_status);
-  if ((st = hb.finish()) != CV_OK) return st;
-  for (int64_t s = 0; s < nseq; ++s)
-    if (status_out[s] == CV_SEQ_INFEASIBLE)
-      return set_err(CV_EINFEASIBLE, "sequence %lld has likelihood 0", (long long)s);
-  return CV_OK;
-}
-
-// ---- expected counts for EM: cv_expected_counts* -----------------------------------------------
-// The posterior entries with the counts request in place of the path: the same checks, staging
-// and INFEASIBLE report; pi_cnt [N] and a_cnt [N][N] come back through st_cnt.
-static cv_status counts_device_entry(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, const int64_t* offsets_dev,
-                                     const int32_t* obs_dev, const double* emis_dev, int64_t ld, bool dense,
-                                     const cv_opts* opts, double* loglik_dev, double* pi_cnt_dev, double* a_cnt_dev,
-                                     double* gamma_dev, uint8_t* status_dev) {
-  if (!h) return set_err(CV_EINVAL, "null handle");
-  if (nseq < 0) return set_err(CV_EINVAL, "nseq < 0");
-  if (!pi_cnt_dev || !a_cnt_dev) return set_err(CV_EINVAL, "null device buffer");
-  if (nseq > 0 && (!offsets_dev || !(dense ? (const void*)emis_dev : (const void*)obs_dev) || !loglik_dev || !status_dev))
-    return set_err(CV_EINVAL, "null device buffer");
-  const cv_opts o = opts ? *opts : default_opts();
-  cv_status st = dense ? posterior_emissions_args_ok(h, ld, o) : posterior_opts_ok(h, o);
-  if (st != CV_OK) return st;
-  CV_LOCK(h);
-  if ((st = set_device(h)) != CV_OK) return st;
-  hipStream_t stream = o.stream ? (hipStream_t)o.stream : h->stream;
-  const EmisSrc src{emis_dev, ld};
-  const CountsReq cnt{pi_cnt_dev, a_cnt_dev};
-  return posterior_device(h, nseq, offsets_host, offsets_dev, dense ? nullptr : obs_dev, o, loglik_dev, nullptr, gamma_dev,
-                          status_dev, stream, dense ? &src : nullptr, nullptr, &cnt);
-}
-
-static cv_status counts_host_entry(cv_hmm* h, int64_t nseq, const int64_t* offsets, const int32_t* obs,
-                                   const double* emis, int64_t ld, bool dense, const cv_opts* opts, double* loglik_out,
-                                   double* pi_cnt_out, double* a_cnt_out, double* gamma_out, uint8_t* status_out) {
-  if (!h) return set_err(CV_EINVAL, "null handle");
-  if (nseq < 0 || !pi_cnt_out || !a_cnt_out) return set_err(CV_EINVAL, "null argument");
-  if (nseq > 0 && (!offsets || !(dense ? (const void*)emis : (const void*)obs) || !loglik_out || !status_out))
-    return set_err(CV_EINVAL, "null argument");
-  cv_opts o = opts ? *opts : default_opts();
-  cv_status st = dense ? posterior_emissions_args_ok(h, ld, o) : posterior_opts_ok(h, o);
-  if (st != CV_OK) return st;
-  CV_LOCK(h);
-  if ((st = set_device(h)) != CV_OK) return st;
-  const size_t N = (size_t)h->N;
-  if (nseq == 0) {  // overwritten, not accumulated
-    std::fill(pi_cnt_out, pi_cnt_out + N, 0.0);
-    std::fill(a_cnt_out, a_cnt_out + N * N, 0.0);
-    return CV_OK;
-  }
-  HostBatch hb{h, nseq, offsets, dense ? nullptr : obs, o.stream ? (hipStream_t)o.stream : h->stream};
-  if ((st = hb.stage(o, 0, 1)) != CV_OK) return st;
-  if (gamma_out && (st = h->st_gamma.ensure(hb.plane() * N * 8)) != CV_OK) return st;
-  if ((st = h->st_cnt.ensure((N + N * N) * 8)) != CV_OK) return st;
-  EmisSrc src{};
-  if (dense && (st = hb.stage_emis(emis, ld, &src)) != CV_OK) return st;
-  const CountsReq cnt{h->st_cnt.as<double>(), h->st_cnt.as<double>() + N};
-  st = posterior_device(h, nseq, offsets, h->st_off.as<int64_t>(), dense ? nullptr : h->st_obs.as<int32_t>(), o,
-                        h->st_score.as<double>(), nullptr, gamma_out ? h->st_gamma.as<double>() : nullptr,
-                        h->st_status.as<uint8_t>(), hb.stream, dense ? &src : nullptr, nullptr, &cnt);
-  if (st != CV_OK) return hb.fail(st);
-  if (gamma_out) hb.fetch_elems(gamma_out, h->st_gamma, N);
-  hb.fetch_seqs(loglik_out, h->st_score);
-  hb.fetch_seqs(status_out, h->st_status);
-  if (hb.err == hipSuccess) hb.err = hipMemcpyAsync(pi_cnt_out, cnt.pi_cnt, N * 8, hipMemcpyDeviceToHost, hb.stream);
-  if (hb.err == hipSuccess) hb.err = hipMemcpyAsync(a_cnt_out, cnt.a_cnt, N * N * 8, hipMemcpyDeviceToHost, hb.stream);
-  if ((st = hb.finish()) != CV_OK) return st;
-  for (int64_t s = 0; s < nseq; ++s)
-    if (status_out[s] == CV_SEQ_INFEASIBLE)
-      return set_err(CV_EINFEASIBLE, "sequence %lld has likelihood 0", (long long)s);
-  return CV_OK;
-}
-
-CV_API cv_status cv_expected_counts_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
-                                           const int64_t* offsets_dev, const int32_t* obs_dev, const cv_opts* opts,
-                                           double* loglik_dev, double* pi_cnt_dev, double* a_cnt_dev, double* gamma_dev,
-                                           uint8_t* status_dev) {
-  return counts_device_entry(h, nseq, offsets_host, offsets_dev, obs_dev, nullptr, 0, false, opts, loglik_dev, pi_cnt_dev,
-                             a_cnt_dev, gamma_dev, status_dev);
-}
-
-CV_API cv_status cv_expected_counts(cv_hmm* h, int64_t nseq, const int64_t* offsets, const int32_t* obs,
-                                    const cv_opts* opts, double* loglik_out, double* pi_cnt_out, double* a_cnt_out,
-                                    double* gamma_out, uint8_t* status_out) {
-  return counts_host_entry(h, nseq, offsets, obs, nullptr, 0, false, opts, loglik_out, pi_cnt_out, a_cnt_out, gamma_out,
-                           status_out);
-}
-
-CV_API cv_status cv_expected_counts_emissions_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
-                                                     const int64_t* offsets_dev, const double* emis_dev, int64_t ld,
-                                                     const cv_opts* opts, double* loglik_dev, double* pi_cnt_dev,
-                                                     double* a_cnt_dev, double* gamma_dev, uint8_t* status_dev) {
-  return counts_device_entry(h, nseq, offsets_host, offsets_dev, nullptr, emis_dev, ld, true, opts, loglik_dev, pi_cnt_dev,
-                             a_cnt_dev, gamma_dev, status_dev);
-}
-
-CV_API cv_status cv_expected_counts_emissions(cv_hmm* h, int64_t nseq, const int64_t* offsets, const double* emis,
-                                              int64_t ld, const cv_opts* opts, double* loglik_out, double* pi_cnt_out,
-                                              double* a_cnt_out, double* gamma_out, uint8_t* status_out) {
-  return counts_host_entry(h, nseq, offsets, nullptr, emis, ld, true, opts, loglik_out, pi_cnt_out, a_cnt_out, gamma_out,
-                           status_out);
-}
-
-// ---- likelihood gradients under emission scores: cv_loglik_grad_emissions* ---------------------
-// The dense expected-counts entries with the gradient request: per-sequence weights (null: all 1)
-// and the gradient rows of E at the caller's stride in place of gamma.
-CV_API cv_status cv_loglik_grad_emissions_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
-                                                 const int64_t* offsets_dev, const double* emis_dev, int64_t ld,
-                                                 const double* weight_dev, const cv_opts* opts, double* loglik_dev,
-                                                 double* pi_grad_dev, double* a_grad_dev, double* emis_grad_dev,
-                                                 int64_t ld_grad, uint8_t* status_dev) {
-  if (!h) return set_err(CV_EINVAL, "null handle");
-  if (nseq < 0) return set_err(CV_EINVAL, "nseq < 0");
-  if (!pi_grad_dev || !a_grad_dev) return set_err(CV_EINVAL, "null device buffer");
-  if (nseq > 0 && (!offsets_dev || !emis_dev || !loglik_dev || !status_dev)) return set_err(CV_EINVAL, "null device buffer");
-  if (emis_grad_dev && ld_grad < h->N)
-    return set_err(CV_EINVAL, "ld_grad = %lld is less than N = %d", (long long)ld_grad, h->N);
-  const cv_opts o = opts ? *opts : default_opts();
-  cv_status st = posterior_emissions_args_ok(h, ld, o);
-  if (st != CV_OK) return st;
-  CV_LOCK(h);
-  if ((st = set_device(h)) != CV_OK) return st;
-  hipStream_t stream = o.stream ? (hipStream_t)o.stream : h->stream;
-  const EmisSrc src{emis_dev, ld};
-  CountsReq cnt{pi_grad_dev, a_grad_dev};
-  cnt.grad = true;
-  cnt.weight = weight_dev;
-  cnt.egrad = emis_grad_dev;
-  cnt.ld_grad = ld_grad;
-  return posterior_device(h, nseq, offsets_host, offsets_dev, nullptr, o, loglik_dev, nullptr, nullptr, status_dev, stream,
-                          &src, nullptr, &cnt);
-}
-
-// Host arrays: the weights ride behind pi_grad and a_grad in st_cnt; the gradient rows are staged
-// compact in st_gamma and copied back at the caller's stride (its columns beyond N stay untouched).
-CV_API cv_status cv_loglik_grad_emissions(cv_hmm* h, int64_t nseq, const int64_t* offsets, const double* emis, int64_t ld,
-                                          const double* weight, const cv_opts* opts, double* loglik_out,
-                                          double* pi_grad_out, double* a_grad_out, double* emis_grad_out,
-                                          int64_t ld_grad, uint8_t* status_out) {
-  if (!h) return set_err(CV_EINVAL, "null handle");
-  if (nseq < 0 || !pi_grad_out || !a_grad_out) return set_err(CV_EINVAL, "null argument");
-  if (nseq > 0 && (!offsets || !emis || !loglik_out || !status_out)) return set_err(CV_EINVAL, "null argument");
-  if (emis_grad_out && ld_grad < h->N)
-    return set_err(CV_EINVAL, "ld_grad = %lld is less than N = %d", (long long)ld_grad, h->N);
-  cv_opts o = opts ? *opts : default_opts();
-  cv_status st = posterior_emissions_args_ok(h, ld, o);
-  if (st != CV_OK) return st;
-  CV_LOCK(h);
-  if ((st = set_device(h)) != CV_OK) return st;
-  const size_t N = (size_t)h->N;
-  if (nseq == 0) {  // overwritten, not accumulated
-    std::fill(pi_grad_out, pi_grad_out + N, 0.0);
-    std::fill(a_grad_out, a_grad_out + N * N, 0.0);
-    return CV_OK;
-  }
-  HostBatch hb{h, nseq, offsets, nullptr, o.stream ? (hipStream_t)o.stream : h->stream};
-  if ((st = hb.stage(o, 0, 1)) != CV_OK) return st;
-  if (emis_grad_out && (st = h->st_gamma.ensure(hb.plane() * N * 8)) != CV_OK) return st;
-  if ((st = h->st_cnt.ensure((N + N * N + (weight ? (size_t)nseq : 0)) * 8)) != CV_OK) return st;
-  EmisSrc src{};
-  if ((st = hb.stage_emis(emis, ld, &src)) != CV_OK) return st;
-  CountsReq cnt{h->st_cnt.as<double>(), h->st_cnt.as<double>() + N};
-  cnt.grad = true;
-  if (weight) {
-    double* const wd = h->st_cnt.as<double>() + N + N * N;
-    HIP_TRY(hipMemcpyAsync(wd, weight, (size_t)nseq * 8, hipMemcpyHostToDevice, hb.stream));
-    cnt.weight = wd;
-  }
-  cnt.egrad = emis_grad_out ? h->st_gamma.as<double>() : nullptr;
-  cnt.ld_grad = (int64_t)N;
-  st = posterior_device(h, nseq, offsets, h->st_off.as<int64_t>(), nullptr, o, h->st_score.as<double>(), nullptr, nullptr,
-                        h->st_status.as<uint8_t>(), hb.stream, &src, nullptr, &cnt);
-  if (st != CV_OK) return hb.fail(st);
-  const size_t rows = (size_t)(hb.total - hb.base);
-  if (emis_grad_out && rows && hb.err == hipSuccess)
-    hb.err = hipMemcpy2DAsync(emis_grad_out + (size_t)hb.base * (size_t)ld_grad, (size_t)ld_grad * 8,
-                              h->st_gamma.as<double>() + (size_t)hb.base * N, N * 8, N * 8, rows, hipMemcpyDeviceToHost,
-                              hb.stream);
-  hb.fetch_seqs(loglik_out, h->st_score);
-  hb.fetch_seqs(status_out, h->st_status);
-  if (hb.err == hipSuccess) hb.err = hipMemcpyAsync(pi_grad_out, cnt.pi_cnt, N * 8, hipMemcpyDeviceToHost, hb.stream);
-  if (hb.err == hipSuccess) hb.err = hipMemcpyAsync(a_grad_out, cnt.a_cnt, N * N * 8, hipMemcpyDeviceToHost, hb.stream);
-  if ((st = hb.finish()) != CV_OK) return st;
-  for (int64_t s = 0; s < nseq; ++s)
-    if (status_out[s] == CV_SEQ_INFEASIBLE)
-      return set_err(CV_EINFEASIBLE, "sequence %lld has likelihood 0", (long long)s);
-  return CV_OK;
-}
-
-// ---- expected counts of the whole discrete model: cv_expected_counts_model* --------------------
-// cv_expected_counts* with per-sequence weights (null: all 1) and the emission counts b_cnt [N][V]:
-// the gradient arm on the handle's own b, its rows w_s gamma scattered by observation (bcount.hip).
-CV_API cv_status cv_expected_counts_model_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
-                                                 const int64_t* offsets_dev, const int32_t* obs_dev,
-                                                 const double* weight_dev, const cv_opts* opts, double* loglik_dev,
-                                                 double* pi_cnt_dev, double* a_cnt_dev, double* b_cnt_dev,
-                                                 double* gamma_dev, uint8_t* status_dev) {
-  if (!h) return set_err(CV_EINVAL, "null handle");
-  if (nseq < 0) return set_err(CV_EINVAL, "nseq < 0");
-  if (!pi_cnt_dev || !a_cnt_dev || !b_cnt_dev) return set_err(CV_EINVAL, "null device buffer");
-  if (nseq > 0 && (!offsets_dev || !obs_dev || !loglik_dev || !status_dev)) return set_err(CV_EINVAL, "null device buffer");
-  const cv_opts o = opts ? *opts : default_opts();
-  cv_status st = posterior_opts_ok(h, o);
-  if (st != CV_OK) return st;
-  CV_LOCK(h);
-  if ((st = set_device(h)) != CV_OK) return st;
-  hipStream_t stream = o.stream ? (hipStream_t)o.stream : h->stream;
-  CountsReq cnt{pi_cnt_dev, a_cnt_dev};
-  cnt.grad = true;
-  cnt.weight = weight_dev;
-  cnt.egrad = gamma_dev;
-  cnt.ld_grad = h->N;
-  cnt.b_cnt = b_cnt_dev;
-  return posterior_device(h, nseq, offsets_host, offsets_dev, obs_dev, o, loglik_dev, nullptr, nullptr, status_dev, stream,
-                          nullptr, nullptr, &cnt);
-}
-
-// Host arrays: pi_cnt, a_cnt, b_cnt and the weights ride in st_cnt, gamma in st_gamma.
-CV_API cv_status cv_expected_counts_model(cv_hmm* h, int64_t nseq, const int64_t* offsets, const int32_t* obs,
-                                          const double* weight, const cv_opts* opts, double* loglik_out,
-                                          double* pi_cnt_out, double* a_cnt_out, double* b_cnt_out, double* gamma_out,
-                                          uint8_t* status_out) {
-  if (!h) return set_err(CV_EINVAL, "null handle");
-  if (nseq < 0 || !pi_cnt_out || !a_cnt_out || !b_cnt_out) return set_err(CV_EINVAL, "null argument");
-  if (nseq > 0 && (!offsets || !obs || !loglik_out || !status_out)) return set_err(CV_EINVAL, "null argument");
-  cv_opts o = opts ? *opts : default_opts();
-  cv_status st = posterior_opts_ok(h, o);
-  if (st != CV_OK) return st;
-  CV_LOCK(h);
-  if ((st = set_device(h)) != CV_OK) return st;
-  const size_t N = (size_t)h->N, V = (size_t)h->V;
-  if (nseq == 0) {  // overwritten, not accumulated
-    std::fill(pi_cnt_out, pi_cnt_out + N, 0.0);
-    std::fill(a_cnt_out, a_cnt_out + N * N, 0.0);
-    std::fill(b_cnt_out, b_cnt_out + N * V, 0.0);
-    return CV_OK;
-  }
-  HostBatch hb{h, nseq, offsets, obs, o.stream ? (hipStream_t)o.stream : h->stream};
-  if ((st = hb.stage(o, 0, 1)) != CV_OK) return st;
-  if (gamma_out && (st = h->st_gamma.ensure(hb.plane() * N * 8)) != CV_OK) return st;
-  if ((st = h->st_cnt.ensure((N + N * N + N * V + (weight ? (size_t)nseq : 0)) * 8)) != CV_OK) return st;
-  CountsReq cnt{h->st_cnt.as<double>(), h->st_cnt.as<double>() + N};
-  cnt.grad = true;
-  cnt.b_cnt = h->st_cnt.as<double>() + N + N * N;
-  if (weight) {
-    double* const wd = cnt.b_cnt + N * V;
-    HIP_TRY(hipMemcpyAsync(wd, weight, (size_t)nseq * 8, hipMemcpyHostToDevice, hb.stream));
-    cnt.weight = wd;
-  }
-  cnt.egrad = gamma_out ? h->st_gamma.as<double>() : nullptr;
-  cnt.ld_grad = (int64_t)N;
-  st = posterior_device(h, nseq, offsets, h->st_off.as<int64_t>(), h->st_obs.as<int32_t>(), o, h->st_score.as<double>(),
-                        nullptr, nullptr, h->st_status.as<uint8_t>(), hb.stream, nullptr, nullptr, &cnt);
-  if (st != CV_OK) return hb.fail(st);
-  if (gamma_out) hb.fetch_elems(gamma_out, h->st_gamma, N);
-  hb.fetch_seqs(loglik_out, h->st_score);
-  hb.fetch_seqs(status_out, h->st_status);
-  if (hb.err == hipSuccess) hb.err = hipMemcpyAsync(pi_cnt_out, cnt.pi_cnt, N * 8, hipMemcpyDeviceToHost, hb.stream);
-  if (hb.err == hipSuccess) hb.err = hipMemcpyAsync(a_cnt_out, cnt.a_cnt, N * N * 8, hipMemcpyDeviceToHost, hb.stream);
-  if (hb.err == hipSuccess) hb.err = hipMemcpyAsync(b_cnt_out, cnt.b_cnt, N * V * 8, hipMemcpyDeviceToHost, hb.stream);
-  if ((st = hb.finish()) != CV_OK) return st;
-  for (int64_t s = 0; s < nseq; ++s)
-    if (status_out[s] == CV_SEQ_INFEASIBLE)
-      return set_err(CV_EINFEASIBLE, "sequence %lld has likelihood 0", (long long)s);
-  return CV_OK;
 }
 
 // ---- consistency-constrained decode --------------------------------------------------------

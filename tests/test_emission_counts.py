@@ -2,6 +2,8 @@
 against an exhaustive enumeration of the state paths, the M-step reestimate_model and the argument
 checks of cviterbi.autograd.discrete_loglik.  No GPU: the kernels are tested in
 test_gpu_emission_counts.py."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -26,6 +28,20 @@ def test_symbols_resolve_and_reject_a_null_handle():
     for name in ("expected_counts_model", "expected_counts_model_device", "reestimate_model"):
         assert callable(getattr(cv, name))
     assert callable(cv.autograd.discrete_loglik)
+
+
+EVAL_ENTRIES = ("cv_posterior_batch", "cv_sample_batch", "cv_posterior_emissions", "cv_expected_counts",
+                "cv_expected_counts_emissions", "cv_loglik_grad_emissions", "cv_expected_counts_model")
+
+
+@pytest.mark.parametrize("name", [e + twin for e in EVAL_ENTRIES for twin in ("", "_device")])
+def test_every_evaluation_entry_rejects_a_null_handle(name):
+    lib = L.lib()
+    f = getattr(lib, name)
+    lib.cv_hmm_set_tuning(None, None, 0)  # another message, so the entry's own is seen
+    assert b"null handle" not in lib.cv_last_error()
+    assert f(None, *[None if t is ctypes.c_void_p else 0 for t in f.argtypes[1:]]) == L.CV_EINVAL
+    assert lib.cv_last_error() == b"null handle"
 
 
 def tiny_model():

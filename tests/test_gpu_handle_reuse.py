@@ -1,6 +1,6 @@
 """GPU: one cv.HMM handle across interleaved entry points and workspace release.
 
-A handle (struct cv_hmm, csrc/cviterbi.cpp) carries lazily built tables, grow-only workspaces
+A handle (struct cv_hmm, csrc/handle.hpp) carries lazily built tables, grow-only workspaces
 shared by unrelated kernels, device counters a call must reset itself, sticky guards and the
 events that order calls on different streams ("Handle state between calls").  Here
 every call on a reused handle must return the bytes the same call returns on a FRESH handle that

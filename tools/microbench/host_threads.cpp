@@ -1,4 +1,4 @@
-// Host-side cost model of parallel_ranges (csrc/cviterbi.cpp) on the GPU box's CPU share:
+// Host-side cost model of parallel_ranges (csrc/handle.hpp) on the GPU box's CPU share:
 // spawning + joining n threads that do nothing, and n threads streaming a 134 MB int32 array
 // (config 5's component array) with a min / max / AND pass.  No GPU.
 #include <algorithm>
