@@ -1,7 +1,9 @@
 // handle.hpp -- the HMM handle (struct cv_hmm) and the host scaffolding shared by the translation
-// units behind include/cviterbi.h: cviterbi.cpp (the handle, decode, constrained, chain, fit and
-// solver entries; the definitions of everything declared here) and evaluate.cpp (the posterior /
-// sampling / counts / gradient entries).  Internal: nothing here is exported.
+// units behind include/cviterbi.h: cviterbi.cpp (the handle and its table builders, the
+// constrained, chain, solver, fit and timing entries; the definitions of everything declared here
+// but the decode core), decode.cpp (the decode / K-best / dense-emission entries; decode_device and
+// decode_host_locked) and evaluate.cpp (the posterior / sampling / counts / gradient entries).
+// Internal: nothing here is exported.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -12,6 +14,7 @@
 #include <cstring>
 #include <mutex>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/cviterbi.h"
@@ -367,8 +370,20 @@ cv_status upload(DevBuf& buf, const void* src, size_t bytes);
 // current bytes, reclaimable).
 uint64_t default_workspace_cap(uint64_t held, uint64_t base);
 cv_status set_device(cv_hmm* h);
-cv_status ensure_f64_tables(cv_hmm* h);
 cv_opts default_opts();
+// The model's device tables by kernel family, each built on first use: the f32 trellis (and its
+// one-wave form), the f64 tables of the generic kernel and the re-scoring, a^T for the generic
+// rows mode (f64 / f32), the exact-f64 trellis, the f32 generic kernel.
+cv_status ensure_trellis_tables(cv_hmm* h);
+cv_status ensure_f64_tables(cv_hmm* h);
+cv_status ensure_at64(cv_hmm* h);
+cv_status ensure_at32(cv_hmm* h);
+cv_status ensure_t64_tables(cv_hmm* h);
+cv_status ensure_g32_tables(cv_hmm* h);
+// Every finite pi/a/b entry in [-2^80, 0] (log-probabilities), and tuning key t64_nonpos on.
+bool model_nonpos(cv_hmm* h);
+// ev[i], created on first use (nullptr: hipEventCreate failed)
+hipEvent_t get_event(std::vector<hipEvent_t>& ev, size_t i);
 
 // Host worker threads for the O(elements) loops of the host API: min(16, hardware threads),
 // tuning key host_threads overrides.
@@ -413,6 +428,21 @@ cv_status host_offsets(int64_t nseq, const int64_t*& offsets_host, const int64_t
 // The longest-first order of a call on its way to the device, through the pinned stage.
 cv_status upload_order(DevBuf& dev, OrderStage& stage, const int32_t* order_host, int64_t nseq, hipStream_t stream,
                        const int32_t** order_dev);
+// The decode workspace a core call runs on: the handle's main one, or the side workspace of a
+// decode running beside another decode_device call of the same handle on another stream.
+struct DecodeWs {
+  DevBuf &main, &last, &order;
+  std::vector<int32_t>& order_host;
+  OrderStage& order_pin;
+  std::vector<hipEvent_t>& ev;
+  hipEvent_t& ws_done;  // the last core call on this workspace has finished
+  bool& ws_rec;
+};
+inline DecodeWs decode_ws(cv_hmm* h, bool side) {
+  auto& s = h->side;
+  if (side) return {s.main, s.last, s.order, s.order_host, s.order_pin, s.ev, s.ws_done, s.ws_rec};
+  return {h->ws_main, h->ws_last, h->ws_order, h->order_host, h->order_pin, h->ev, h->ws_done, h->ws_rec};
+}
 // The nev timing events of a call, evv[*eb ...]: from 0 (each call overwrites the last), or
 // appended after the calls already timed since cv_timing_begin.  side_ws: the side workspace's
 // own events, no bookkeeping.
@@ -435,6 +465,37 @@ struct EmisSrc {
   const double* p;
   int64_t ld;
 };
+
+// The options of decode_device beyond a plain decode; every caller names only what it sets.
+struct DecodeReq {
+  const void* resume_rows = nullptr;  // the constrained decode's resume rows (the kernel's real type)
+  // the handle's second workspace (h->side), no timing / last-call bookkeeping -- a decode
+  // running beside another decode_device call of the same handle on another stream
+  bool side_ws = false;
+  // the parallel CPSolver chain (row-A0 f64 trellis or the f64 generic rows mode): each chunk's
+  // backtrack computes its certificates (or a cp_cert pass reads its rows and paths) -> [nseq][2]
+  double* cp_cert = nullptr;
+  const double* cp_init = nullptr;  // the chain's speculative re-decodes: start offsets in,
+  double* cp_last = nullptr;        // last values out
+  // h->chunk_ev[i] is recorded after chunk i's backtrack (its paths written, before any
+  // certificate pass) and its sequence range [s0, s1) appended
+  std::vector<std::pair<int64_t, int64_t>>* chunks_out = nullptr;
+  // cv_decode_emissions* (f64 only; the caller has checked the options, emissions_opts_ok): the
+  // emissions of every element come from this dense array instead of the handle's b through
+  // obs_dev (ignored, may be null); each chunk's rows are staged beside its delta rows
+  const EmisSrc* emis = nullptr;
+  // cv_decode_batch[_device] only: the f64 trellis may keep sparse low planes (tuning key
+  // t64_lo_every) and records the resolver's counters (cv_last_t64_stats)
+  bool batch_api = false;
+};
+// Core device-side decode (decode.cpp).  All pointers are device pointers except offsets_host.
+cv_status decode_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, const int64_t* offsets_dev,
+                        const int32_t* obs_dev, const cv_opts& o, int32_t* path_dev, double* score_dev,
+                        uint8_t* status_dev, hipStream_t stream, const DecodeReq& rq = DecodeReq{});
+// Host-pointer decode (decode.cpp); the caller holds h->mu and has selected the device.
+cv_status decode_host_locked(cv_hmm* h, int64_t nseq, const int64_t* offsets, const int32_t* obs, cv_opts o,
+                             int32_t* path_out, double* score_out, uint8_t* status_out, bool obs_staged = false,
+                             bool forced_staged = false, bool batch_api = false);
 
 // CV_EINFEASIBLE for the first sequence of a fetched batch with status CV_SEQ_INFEASIBLE:
 // "sequence <s> <what>".

@@ -277,7 +277,7 @@ def test_cp_trellis_waves_seqs_rows(gpu, n):
 @pytest.mark.parametrize("n", [193, 256])
 def test_column_split_four_pairs(gpu, n):
     """t64_rs = 0, t64_s = 4 at NP = 256: fwd_cs<4, 4> hands the batch to fwd_w2<8> (trellis64.hip),
-    where the row split is off (rs_mode false), so with wg_ok (equal lengths: cviterbi.cpp sets it
+    where the row split is off (rs_mode false), so with wg_ok (equal lengths: decode.cpp sets it
     when 8 tmin >= 7 tmax) or t64_wg_force = 1 (the ragged batch) the only launch left is
     trellis_fwd_f64<2, 8, 8, false, false, 2, true, 2, 1, true, 4, 2>: four pairs of waves per
     workgroup, a barrier per step, units that finish at different steps.  t64_s = 4 also keeps the
