@@ -540,7 +540,8 @@ CV_API cv_status cv_hmm_release_workspaces(cv_hmm* h) {
                     &h->chainb.rpsi, &h->chainb.rows, &h->chainb.small, &h->chainb.rpath, &h->chainb.soff,
                     &h->chainb.sobs, &h->chainb.spath, &h->chainb.sres, &h->chainb.sinit, &h->chainb.slast,
                     &h->chainb.spsi, &h->ps_rows, &h->ps_order, &h->ps_kshift, &h->st_gamma, &h->ps_xi_part,
-                    &h->ps_xi_s, &h->ps_g0, &h->st_cnt, &h->ps_bc_acc, &h->ps_bc_sort, &h->ps_bc_part, &h->kb_bp,
+                    &h->ps_xi_s, &h->ps_g0, &h->st_cnt, &h->ps_bc_acc, &h->ps_bc_sort, &h->ps_bc_part, &h->ps_gauss,
+                    &h->ps_gm_part, &h->ps_gm_acc, &h->ps_gm_ok, &h->kb_bp,
                     &h->kb_last, &h->kb_order, &h->kb_end, &h->st_count,
                     &h->st_emis, &h->fx_cert, &h->fx_idx, &h->fx_obs2, &h->fx_path2, &h->fx_score2, &h->fx_status2,
                     &h->ru_mu, &h->ru_r, &h->ru_e})

@@ -1,9 +1,10 @@
 // evaluate.cpp -- the evaluation (sum-product) entries of the C ABI (include/cviterbi.h):
 // cv_posterior_batch, cv_sample_batch, cv_posterior_emissions, cv_expected_counts,
-// cv_expected_counts_emissions, cv_loglik_grad_emissions, cv_expected_counts_model and their
-// _device twins.  One core (posterior_device: a workspace plan, the arms of a chunk, a short
-// loop), one path for the _device entries and one for the host entries; each exported function is
-// its argument checks and a filled request.  The handle and the shared scaffolding: handle.hpp.
+// cv_expected_counts_emissions, cv_loglik_grad_emissions, cv_expected_counts_model,
+// cv_gauss_emissions, cv_expected_counts_gauss and their _device twins.  One core
+// (posterior_device: a workspace plan, the arms of a chunk, a short loop), one path for the _device
+// entries and one for the host entries; each exported function is its argument checks and a filled
+// request.  The handle and the shared scaffolding: handle.hpp.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -14,6 +15,7 @@
 #include "handle.hpp"
 #include "kernels/bcount.h"
 #include "kernels/emis.h"
+#include "kernels/gauss.h"
 #include "kernels/posterior.h"
 #include "kernels/sample.h"
 
@@ -75,6 +77,16 @@ struct SampleReq {
   int32_t* path;  // device, [draws][offsets[nseq]]
   double* score;  // device, [draws][nseq], nullable
 };
+// cv_expected_counts_gauss*: the Gaussian arm of the counts request (gauss.hip).  The density kernel
+// fills a chunk-local workspace the staging reads (EmisSrc::chunk_local), and the rows w_s gamma of
+// the gradient arm meet Phi = [1 | y | y^2] in the moment GEMM
+struct GaussReq {
+  const double* x;    // device, element e at x + e * ldx, D values
+  int64_t ldx;
+  int D;
+  const double* tab;  // device: the call's tables (cvg::gauss_table_doubles)
+  double *g_cnt, *m1, *m2;  // device, [N], [N][D], [N][D]
+};
 // cv_expected_counts*: the counts arm of the backward pass and the kernels behind it
 struct CountsReq {
   double* pi_cnt;  // device, [N]
@@ -89,6 +101,8 @@ struct CountsReq {
   // grad set -- the rows w_s gamma the gradient arm stores are what the scatter by observation adds.
   // egrad (ld_grad = N) is then the caller's gamma; null: a chunk-local workspace takes the rows
   double* b_cnt = nullptr;  // device, nullable, [N][V]
+  // cv_expected_counts_gauss*: with grad set and egrad as for b_cnt; PostReq::emis is chunk-local
+  const GaussReq* gauss = nullptr;
 };
 // What one call asks of posterior_device, filled by field name: the outputs (device pointers), the
 // stream, and at most one of each mode -- dense emissions, the sampler, the counts arm.
@@ -113,15 +127,16 @@ struct Batch {
 
 // The workspace of a call: chunks of whole sequences whose per-element rows fit the cap, and
 // ps_rows carved into [max_elems][NP] forward rows (store), [max_elems][NP] U rows (counts),
-// [max_elems][NP] staged emission rows (emis), [max_elems][NP] rows w_s gamma (emission counts
-// without the caller's gamma), [max_elems] inv (counts), [max_elems] int32 observation indices
-// (emis); NP * 8 is a multiple of 512.  A pointer is null when its mode is off.
+// [max_elems][NP] staged emission rows (emis), [max_elems][NP] rows w_s gamma (emission counts or
+// Gaussian moments without the caller's gamma), [max_elems][NP] log10 densities (Gaussian),
+// [max_elems] inv (counts), [max_elems] int32 observation indices (emis); NP * 8 is a multiple of
+// 512.  A pointer is null when its mode is off.
 struct PostPlan {
   bool store = false;  // any row is kept: everything but the scoring mode
-  bool bc_ws = false;  // emission counts: the rows w_s gamma go to the workspace
-  uint64_t row_bytes = 0, per_elem = 0, part_cap = 0, max_elems = 0;
+  bool bc_ws = false;  // emission counts, Gaussian moments: the rows w_s gamma go to the workspace
+  uint64_t row_bytes = 0, per_elem = 0, part_cap = 0, gm_cap = 0, max_elems = 0;
   std::vector<cvplan::Chunk> chunks;
-  double *ws_rows = nullptr, *ws_urows = nullptr, *ws_emis = nullptr, *ws_g = nullptr, *ws_inv = nullptr;
+  double *ws_rows = nullptr, *ws_urows = nullptr, *ws_emis = nullptr, *ws_g = nullptr, *ws_dens = nullptr, *ws_inv = nullptr;
   int32_t* ws_idx = nullptr;
 };
 
@@ -133,11 +148,12 @@ cv_status plan_workspace(cv_hmm* h, const Batch& bt, const cv_opts& o, const Pos
   const int64_t* offsets_host = bt.offsets_host;
   cv_status st;
   p.store = rq.path || rq.gamma || rq.smp || cnt;
-  p.bc_ws = cnt && cnt->b_cnt && !cnt->egrad;
+  const GaussReq* gs = cnt ? cnt->gauss : nullptr;
+  p.bc_ws = cnt && (cnt->b_cnt || gs) && !cnt->egrad;
   const uint64_t row_bytes = p.row_bytes = (uint64_t)np * 8;
   // counts: the U row and inv of every element beside its forward row
   const uint64_t per_elem = p.per_elem =
-      (p.store ? row_bytes : 0) + (cnt ? row_bytes + 8 : 0) + (emis ? row_bytes + 4 : 0) + (p.bc_ws ? row_bytes : 0);
+      (p.store ? row_bytes : 0) + (cnt ? row_bytes + 8 : 0) + (emis ? row_bytes + 4 : 0) + (p.bc_ws ? row_bytes : 0) + (gs ? row_bytes : 0);
   if (per_elem == 0) {
     p.chunks.emplace_back(0, bt.nseq);
   } else {
@@ -149,6 +165,12 @@ cv_status plan_workspace(cv_hmm* h, const Batch& bt, const cv_opts& o, const Pos
       const uint64_t most = std::min<uint64_t>(cvp::kXiPartCap, (uint64_t)cvp::kXiMaxParts * np * row_bytes);
       p.part_cap = cap >= 2 * most ? most : cap / 2;
       cap -= p.part_cap;
+    }
+    // ... and the moment GEMM's, by the same rule on what is left
+    if (gs) {
+      const uint64_t most = std::min<uint64_t>(cvg::kGmPartCap, (uint64_t)cvg::kGmMaxParts * cvg::gm_padded_width(gs->D) * row_bytes);
+      p.gm_cap = cap >= 2 * most ? most : cap / 2;
+      cap -= p.gm_cap;
     }
     uint64_t elem_cap = cap / per_elem;
     if (emis) {  // the staged rows of a sequence cannot be split, and a chunk is indexed by int32
@@ -174,6 +196,7 @@ cv_status plan_workspace(cv_hmm* h, const Batch& bt, const cv_opts& o, const Pos
   p.ws_urows = take_rows(cnt != nullptr, (uint64_t)np);
   p.ws_emis = take_rows(emis != nullptr, (uint64_t)np);
   p.ws_g = take_rows(p.bc_ws, (uint64_t)np);
+  p.ws_dens = take_rows(gs != nullptr, (uint64_t)np);
   p.ws_inv = take_rows(cnt != nullptr, 1);
   p.ws_idx = emis ? reinterpret_cast<int32_t*>(ws_next) : nullptr;
   return CV_OK;
@@ -184,6 +207,7 @@ struct CountsArm {
   int64_t xi_key = 0;  // tuning key xi_part_rows
   int64_t bc_key = 0;  // tuning key bcnt_part_rows
   cvb::BcntArgs bq{};  // emission counts: what every chunk's launch shares
+  int64_t gm_key = 0;  // tuning key gm_part_rows
 };
 
 // Counts: the GEMM's partial tiles of the largest chunk, the accumulator ps_xi_s (zeroed here) and
@@ -249,13 +273,71 @@ cv_status prepare_emission_counts(cv_hmm* h, const Batch& bt, const PostPlan& pl
   return CV_OK;
 }
 
+// Gaussian moments: the partial tiles of the largest chunk, the row flags, the accumulator ps_gm_acc
+// (zeroed here).
+cv_status prepare_gauss(cv_hmm* h, const Batch& bt, const PostPlan& plan, const PostReq& rq, CountsArm* arm) {
+  const int np = h->pnp, wp = cvg::gm_padded_width(rq.cnt->gauss->D);
+  cv_status st;
+  arm->gm_key = cvk::tuning().gm_part_rows;
+  int64_t most_parts = 1;
+  for (const auto& c : plan.chunks) {
+    const int64_t rows = bt.offsets_host[c.second] - bt.offsets_host[c.first];
+    const int64_t per = cvg::gm_part_rows(rows, np, wp, arm->gm_key, plan.gm_cap);
+    most_parts = std::max(most_parts, (rows + per - 1) / per);
+  }
+  if ((st = h->ps_gm_part.ensure((size_t)most_parts * wp * plan.row_bytes)) != CV_OK) return st;
+  if ((st = h->ps_gm_acc.ensure((size_t)wp * plan.row_bytes)) != CV_OK) return st;
+  if ((st = h->ps_gm_ok.ensure((size_t)plan.max_elems * 4)) != CV_OK) return st;
+  HIP_TRY(hipMemsetAsync(h->ps_gm_acc.p, 0, (size_t)wp * plan.row_bytes, rq.stream));
+  return CV_OK;
+}
+
+// The device tables of a Gaussian call inside h->ps_gauss (cvg::gauss_table_doubles).
+struct GaussTab {
+  const double *c, *mu_t, *w_t, *center;
+};
+GaussTab gauss_tab(const double* tab, int N, int D) {
+  const size_t dp = (size_t)cvg::gauss_padded_dims(D);
+  return GaussTab{tab, tab + N, tab + N + dp * (size_t)N, tab + N + 2 * dp * (size_t)N};
+}
+
+// The density kernel over `nrows` rows of x into out (row stride ld).
+cv_status launch_density(cv_hmm* h, const double* tab, const double* x, int64_t ldx, int D, int64_t nrows, double* out,
+                         int64_t ld, hipStream_t stream) {
+  const GaussTab t = gauss_tab(tab, h->N, D);
+  cvg::GaussArgs ga{};
+  ga.x = x;
+  ga.ldx = ldx;
+  ga.nrows = nrows;
+  ga.D = D;
+  ga.DP = cvg::gauss_padded_dims(D);
+  ga.nstates = h->N;
+  ga.c = t.c;
+  ga.mu_t = t.mu_t;
+  ga.w_t = t.w_t;
+  ga.out = out;
+  ga.ld = ld;
+  const hipError_t err = cvg::launch_gauss_emis(ga, h->cus, stream);
+  if (err != hipSuccess) return set_err(CV_EDEVICE, "Gaussian density launch failed: %s", hipGetErrorString(err));
+  return CV_OK;
+}
+
 // Dense emissions: the chunk's rows staged in probability space behind its forward rows; g then
-// reads them as its emission table, one row per element.
+// reads them as its emission table, one row per element.  A chunk-local source (the Gaussian arm)
+// is first filled by the density kernel: row 0 of its workspace is element e0.
 cv_status stage_chunk_emissions(cv_hmm* h, const PostReq& rq, const PostPlan& plan, const Batch& bt, cvp::PostArgs* g) {
   const int64_t e0 = bt.offsets_host[g->seq_begin], e1 = bt.offsets_host[g->seq_end];
   cvem::EmisLinArgs eg{};
   eg.src = rq.emis->p;
   eg.ld = rq.emis->ld;
+  if (rq.emis->chunk_local) {
+    const GaussReq* gs = rq.cnt->gauss;
+    const cv_status st = launch_density(h, gs->tab, gs->x + (size_t)e0 * (size_t)gs->ldx, gs->ldx, gs->D, e1 - e0,
+                                        plan.ws_dens, h->pnp, rq.stream);
+    if (st != CV_OK) return st;
+    eg.src = rebased<const double>(plan.ws_dens, e0, (size_t)h->pnp);
+    eg.ld = h->pnp;
+  }
   eg.e0 = e0;
   eg.nrows = e1 - e0;
   eg.nstates = h->N;
@@ -362,6 +444,32 @@ cv_status counts_chunk(cv_hmm* h, const PostReq& rq, const PostPlan& plan, const
     err = cvb::launch_bcnt_chunk(b, rq.stream);
     if (err == hipSuccess && last) err = cvb::launch_bcnt_final(arm.bq.acc, h->V, h->N, np, cnt->b_cnt, rq.stream);
   }
+  if (err == hipSuccess && cnt->gauss) {
+    const GaussReq* gs = cnt->gauss;
+    cvg::GmArgs m{};
+    m.offsets = bt.offsets_dev;
+    m.status = rq.status;
+    m.seq_begin = g.seq_begin;
+    m.seq_end = g.seq_end;
+    m.elem_base = g.elem_base;
+    m.nrows = x.nrows;
+    m.g = plan.bc_ws ? plan.ws_g : cnt->egrad + (size_t)g.elem_base * (size_t)h->N;
+    m.ldg = g.ld_grad;
+    m.x = gs->x;
+    m.ldx = gs->ldx;
+    m.center = gauss_tab(gs->tab, h->N, gs->D).center;
+    m.D = gs->D;
+    m.wp = cvg::gm_padded_width(gs->D);
+    m.nstates = h->N;
+    m.np = np;
+    m.rowok = h->ps_gm_ok.as<int32_t>();
+    m.part_rows = cvg::gm_part_rows(m.nrows, np, m.wp, arm.gm_key, plan.gm_cap);
+    m.nparts = (m.nrows + m.part_rows - 1) / m.part_rows;
+    m.part = h->ps_gm_part.as<double>();
+    m.acc = h->ps_gm_acc.as<double>();
+    err = cvg::launch_gm_chunk(m, rq.stream);
+    if (err == hipSuccess && last) err = cvg::launch_gm_final(m.acc, h->N, gs->D, m.wp, gs->g_cnt, gs->m1, gs->m2, rq.stream);
+  }
   if (err != hipSuccess) return set_err(CV_EDEVICE, "expected-counts launch failed: %s", hipGetErrorString(err));
   return CV_OK;
 }
@@ -383,7 +491,10 @@ cv_status counts_chunk(cv_hmm* h, const PostReq& rq, const PostPlan& plan, const
 // pass is the gradient arm's; nothing else differs.  cnt->b_cnt (cv_expected_counts_model*; with
 // cnt->grad, the handle's own b): the rows w_s gamma of the gradient arm go to cnt->egrad (the
 // caller's gamma, stride N) or, when that is null, to a chunk-local workspace (8 NP bytes per
-// element more, under the cap).
+// element more, under the cap).  cnt->gauss (cv_expected_counts_gauss*; with cnt->grad and a
+// chunk-local rq.emis): each chunk's log10 densities are computed into a workspace of their own
+// (8 NP bytes per element more) before the staging reads them, and the rows w_s gamma -- placed as
+// for b_cnt -- meet Phi = [1 | y | y^2] in the moment GEMM (its partial tiles under the cap too).
 cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, const int64_t* offsets_dev,
                            const int32_t* obs_dev, const cv_opts& o, const PostReq& rq) {
   const CountsReq* cnt = rq.cnt;
@@ -404,6 +515,11 @@ cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
     HIP_TRY(hipMemsetAsync(cnt->pi_cnt, 0, (size_t)h->N * 8, stream));
     HIP_TRY(hipMemsetAsync(cnt->a_cnt, 0, (size_t)h->N * h->N * 8, stream));
     if (cnt->b_cnt) HIP_TRY(hipMemsetAsync(cnt->b_cnt, 0, (size_t)h->N * (size_t)h->V * 8, stream));
+    if (cnt->gauss) {
+      HIP_TRY(hipMemsetAsync(cnt->gauss->g_cnt, 0, (size_t)h->N * 8, stream));
+      HIP_TRY(hipMemsetAsync(cnt->gauss->m1, 0, (size_t)h->N * cnt->gauss->D * 8, stream));
+      HIP_TRY(hipMemsetAsync(cnt->gauss->m2, 0, (size_t)h->N * cnt->gauss->D * 8, stream));
+    }
   }
   if (nseq == 0) return CV_OK;
   if (h->ws_rec) HIP_TRY(hipStreamWaitEvent(stream, h->ws_done, 0));
@@ -411,6 +527,10 @@ cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
   const bool bc = cnt && cnt->b_cnt;
   if (bc && (rq.emis || !cnt->grad || !obs_dev || rq.gamma || (cnt->egrad && cnt->ld_grad != h->N)))
     return set_err(CV_EINTERNAL, "emission counts: the discrete model under the gradient arm only");
+  const bool gs = cnt && cnt->gauss;
+  if (gs && (bc || !rq.emis || !rq.emis->chunk_local || !cnt->grad || rq.gamma || (cnt->egrad && cnt->ld_grad != h->N)))
+    return set_err(CV_EINTERNAL, "Gaussian moments: chunk-local densities under the gradient arm only");
+  if (!gs && rq.emis && rq.emis->chunk_local) return set_err(CV_EINTERNAL, "chunk-local emissions without their source");
   if (bc && h->V > INT32_MAX) return set_err(CV_ELIMIT, "emission counts cover V <= %d (V=%lld)", INT32_MAX, (long long)h->V);
   const Batch bt{nseq, offsets_host, offsets_dev, obs_dev};
   PostPlan plan;
@@ -418,6 +538,7 @@ cv_status posterior_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
   CountsArm arm;
   if (cnt && (st = prepare_counts(h, bt, plan, stream, &arm)) != CV_OK) return st;
   if (bc && (st = prepare_emission_counts(h, bt, plan, rq, &arm)) != CV_OK) return st;
+  if (gs && (st = prepare_gauss(h, bt, plan, rq, &arm)) != CV_OK) return st;
   if (rq.emis) {
     if ((st = h->ps_kshift.ensure((size_t)nseq * 8)) != CV_OK) return st;
     HIP_TRY(hipMemsetAsync(h->ps_kshift.p, 0, (size_t)nseq * 8, stream));
@@ -521,6 +642,55 @@ cv_status device_entry(cv_hmm* h, int64_t nseq, const int64_t* offsets_host, con
   return posterior_device(h, nseq, offsets_host, offsets_dev, obs_dev, o, rq);
 }
 
+// The argument checks of the Gaussian entries, made before any device work.
+cv_status gauss_args_ok(const cv_hmm* h, int64_t ldx, int64_t D, const double* mean, const double* var) {
+  if (D < 1) return set_err(CV_EINVAL, "D = %lld is less than 1", (long long)D);
+  if (D > cvg::kGaussMaxDims) return set_err(CV_ELIMIT, "the Gaussian kernels cover D <= %d (D=%lld)", cvg::kGaussMaxDims, (long long)D);
+  if (ldx < D) return set_err(CV_EINVAL, "ldx = %lld is less than D = %lld", (long long)ldx, (long long)D);
+  if (!mean || !var) return set_err(CV_EINVAL, "null mean or var");
+  const int64_t n = (int64_t)h->N * D;
+  int64_t k = first_bad(0, n, [&](int64_t i) { return !std::isfinite(mean[i]); });
+  if (k >= 0) return set_err(CV_EINVAL, "mean[%lld][%lld] is not finite", (long long)(k / D), (long long)(k % D));
+  k = first_bad(0, n, [&](int64_t i) { return !(var[i] >= 1e-300 && var[i] <= 1e300); });
+  if (k >= 0)
+    return set_err(CV_EINVAL, "var[%lld][%lld] = %g is outside [1e-300, 1e300]", (long long)(k / D), (long long)(k % D), var[k]);
+  return CV_OK;
+}
+
+// The tables of a Gaussian call, in f64 on the host: w = 1 / var (one division per entry), c_j =
+// -1/2 sum_d log10(2 pi var_jd) in ascending d, mean and w transposed to [DP][N] and zero padded,
+// center [DP] (null: zeros).  Through the pinned stage to h->ps_gauss on `stream`, behind the last
+// call that used the workspaces.
+cv_status upload_gauss_tables(cv_hmm* h, int D, const double* mean, const double* var, const double* center,
+                              hipStream_t stream, const double** tab) {
+  const size_t N = (size_t)h->N, dp = (size_t)cvg::gauss_padded_dims(D), n = cvg::gauss_table_doubles(h->N, D);
+  cv_status st = h->ps_gauss.ensure(n * 8);
+  if (st != CV_OK) return st;
+  double* const pin = reinterpret_cast<double*>(h->gs_pin.acquire(2 * n));
+  if (!pin) return set_err(CV_ENOMEM, "pinned staging of %zu table entries failed", n);
+  std::memset(pin, 0, n * 8);
+  double *c = pin, *mu_t = pin + N, *w_t = mu_t + dp * N, *cen = w_t + dp * N;
+  constexpr double kTwoPi = 6.283185307179586476925;
+  parallel_ranges((int64_t)N, [&](int, int64_t lo, int64_t hi) {
+    for (int64_t j = lo; j < hi; ++j) {
+      double sum = 0.0;
+      for (int d = 0; d < D; ++d) {
+        const double v = var[(size_t)j * D + d];
+        sum += std::log10(kTwoPi * v);
+        mu_t[(size_t)d * N + j] = mean[(size_t)j * D + d];
+        w_t[(size_t)d * N + j] = 1.0 / v;
+      }
+      c[j] = -0.5 * sum;
+    }
+  }, std::max<int64_t>(1, 65536 / D));
+  for (int d = 0; center && d < D; ++d) cen[d] = center[d];
+  if (h->ws_rec) HIP_TRY(hipStreamWaitEvent(stream, h->ws_done, 0));
+  HIP_TRY(hipMemcpyAsync(h->ps_gauss.p, pin, n * 8, hipMemcpyHostToDevice, stream));
+  HIP_TRY(h->gs_pin.release(stream));
+  *tab = h->ps_gauss.as<const double>();
+  return CV_OK;
+}
+
 // What a host entry wants back in the caller's arrays (null: not asked).
 struct HostOut {
   double* loglik;
@@ -533,12 +703,19 @@ struct HostOut {
   double *pi_cnt = nullptr, *a_cnt = nullptr, *b_cnt = nullptr;
   bool grad = false;
   const double* weight = nullptr;
+  // cv_expected_counts_gauss (g_cnt set; with grad): the observation vectors x (host, element e at
+  // x + e * ldx), the model's rows and the center (nullable), and the moments back
+  const double *x = nullptr, *mean = nullptr, *var = nullptr, *center = nullptr;
+  int64_t ldx = 0;
+  int D = 0;
+  double *g_cnt = nullptr, *m1 = nullptr, *m2 = nullptr;
 };
 
 // A host entry after its argument checks: the batch through the handle's staging (HostBatch;
 // obs or the dense rows emis, whichever is given), the core on the st_* buffers, the results
 // back, and CV_EINFEASIBLE for the first sequence of likelihood 0.  The counts ride in st_cnt as
-// [pi N][a N * N][b N * V if asked][weight nseq if given], gamma compact in st_gamma.
+// [pi N][a N * N][b N * V if asked][g_cnt N, m1 N * D, m2 N * D if asked][weight nseq if given],
+// gamma compact in st_gamma; the rows of x compact in st_emis.
 cv_status host_entry(cv_hmm* h, int64_t nseq, const int64_t* offsets, const int32_t* obs, const double* emis,
                      int64_t ld, cv_opts o, const HostOut& out) {
   CV_LOCK(h);
@@ -549,22 +726,44 @@ cv_status host_entry(cv_hmm* h, int64_t nseq, const int64_t* offsets, const int3
     if (out.pi_cnt) std::fill(out.pi_cnt, out.pi_cnt + N, 0.0);
     if (out.a_cnt) std::fill(out.a_cnt, out.a_cnt + N * N, 0.0);
     if (out.b_cnt) std::fill(out.b_cnt, out.b_cnt + N * V, 0.0);
+    if (out.g_cnt) std::fill(out.g_cnt, out.g_cnt + N, 0.0);
+    if (out.g_cnt) std::fill(out.m1, out.m1 + N * (size_t)out.D, 0.0);
+    if (out.g_cnt) std::fill(out.m2, out.m2 + N * (size_t)out.D, 0.0);
     return CV_OK;
   }
   // the observations are range-checked on the device (CV_SEQ_BADOBS), as in the _device variants
   HostBatch hb{h, nseq, offsets, obs, call_stream(h, o)};
   if ((st = hb.stage(o, out.path ? 1 : 0, 1)) != CV_OK) return st;
   if (out.gamma && (st = h->st_gamma.ensure(hb.plane() * N * 8)) != CV_OK) return st;
-  const size_t nb = out.b_cnt ? N * V : 0;
+  const size_t ND = N * (size_t)out.D, nb = out.b_cnt ? N * V : out.g_cnt ? N + 2 * ND : 0;
   if (out.pi_cnt && (st = h->st_cnt.ensure((N + N * N + nb + (out.weight ? (size_t)nseq : 0)) * 8)) != CV_OK) return st;
   EmisSrc src{};
   if (emis && (st = hb.stage_emis(emis, ld, &src)) != CV_OK) return st;
+  GaussReq gs{};
+  if (out.g_cnt) {
+    const size_t Dd = (size_t)out.D, xrows = (size_t)(hb.total - hb.base);
+    if ((st = h->st_emis.ensure(std::max<size_t>(xrows, 1) * Dd * 8)) != CV_OK) return st;
+    if (xrows > 0)
+      HIP_TRY(hipMemcpy2DAsync(h->st_emis.p, Dd * 8, out.x + (size_t)hb.base * (size_t)out.ldx, (size_t)out.ldx * 8, Dd * 8,
+                               xrows, hipMemcpyHostToDevice, hb.stream));
+    gs.x = rebased(h->st_emis.as<const double>(), hb.base, Dd);
+    gs.ldx = out.D;
+    gs.D = out.D;
+    if ((st = upload_gauss_tables(h, out.D, out.mean, out.var, out.center, hb.stream, &gs.tab)) != CV_OK) return st;
+    src.chunk_local = true;
+  }
   double* const gamma_dev = out.gamma ? h->st_gamma.as<double>() : nullptr;
   CountsReq cnt{nullptr, nullptr};
   if (out.pi_cnt) {
     cnt.pi_cnt = h->st_cnt.as<double>();
     cnt.a_cnt = cnt.pi_cnt + N;
     if (out.b_cnt) cnt.b_cnt = cnt.a_cnt + N * N;
+    if (out.g_cnt) {
+      gs.g_cnt = cnt.a_cnt + N * N;
+      gs.m1 = gs.g_cnt + N;
+      gs.m2 = gs.m1 + ND;
+      cnt.gauss = &gs;
+    }
     if (out.weight) {
       double* const wd = cnt.a_cnt + N * N + nb;
       HIP_TRY(hipMemcpyAsync(wd, out.weight, (size_t)nseq * 8, hipMemcpyHostToDevice, hb.stream));
@@ -582,7 +781,7 @@ cv_status host_entry(cv_hmm* h, int64_t nseq, const int64_t* offsets, const int3
   rq.gamma = out.grad ? nullptr : gamma_dev;
   rq.status = h->st_status.as<uint8_t>();
   rq.stream = hb.stream;
-  rq.emis = emis ? &src : nullptr;
+  rq.emis = emis || out.g_cnt ? &src : nullptr;
   rq.cnt = out.pi_cnt ? &cnt : nullptr;
   st = posterior_device(h, nseq, offsets, h->st_off.as<int64_t>(), obs ? h->st_obs.as<int32_t>() : nullptr, o, rq);
   if (st != CV_OK) return hb.fail(st);
@@ -597,6 +796,9 @@ cv_status host_entry(cv_hmm* h, int64_t nseq, const int64_t* offsets, const int3
   if (out.pi_cnt) hb.fetch_n(out.pi_cnt, cnt.pi_cnt, N);
   if (out.pi_cnt) hb.fetch_n(out.a_cnt, cnt.a_cnt, N * N);
   if (out.b_cnt) hb.fetch_n(out.b_cnt, cnt.b_cnt, N * V);
+  if (out.g_cnt) hb.fetch_n(out.g_cnt, (const double*)gs.g_cnt, N);
+  if (out.g_cnt) hb.fetch_n(out.m1, (const double*)gs.m1, ND);
+  if (out.g_cnt) hb.fetch_n(out.m2, (const double*)gs.m2, ND);
   if ((st = hb.finish()) != CV_OK) return st;
   return report_infeasible(nseq, out.status, "has likelihood 0");
 }
@@ -909,6 +1111,126 @@ CV_API cv_status cv_expected_counts_model(cv_hmm* h, int64_t nseq, const int64_t
   out.grad = true;
   out.weight = weight;
   return host_entry(h, nseq, offsets, obs, nullptr, 0, o, out);
+}
+
+// ---- Gaussian emissions: cv_gauss_emissions*, cv_expected_counts_gauss* ------------------------
+CV_API cv_status cv_gauss_emissions_device(cv_hmm* h, int64_t nrows, const double* x_dev, int64_t ldx, int64_t D,
+                                           const double* mean, const double* var, const cv_opts* opts,
+                                           double* emis_dev, int64_t ld) {
+  if (!h) return set_err(CV_EINVAL, "null handle");
+  if (nrows < 0) return set_err(CV_EINVAL, "nrows < 0");
+  if (ld < h->N) return set_err(CV_EINVAL, "ld = %lld is less than N = %d", (long long)ld, h->N);
+  cv_status st = gauss_args_ok(h, ldx, D, mean, var);
+  if (st != CV_OK) return st;
+  if (nrows > 0 && (!x_dev || !emis_dev)) return set_err(CV_EINVAL, "null device buffer");
+  if (nrows == 0) return CV_OK;
+  const cv_opts o = opts ? *opts : default_opts();
+  CV_LOCK(h);
+  if ((st = set_device(h)) != CV_OK) return st;
+  const hipStream_t stream = call_stream(h, o);
+  const double* tab = nullptr;
+  if ((st = upload_gauss_tables(h, (int)D, mean, var, nullptr, stream, &tab)) != CV_OK) return st;
+  if ((st = launch_density(h, tab, x_dev, ldx, (int)D, nrows, emis_dev, ld, stream)) != CV_OK) return st;
+  return end_call(h, false, 0, stream);  // the tables stay in use until here
+}
+
+// Host arrays: the rows of x go compact to st_emis, the scores come back at the caller's stride.
+CV_API cv_status cv_gauss_emissions(cv_hmm* h, int64_t nrows, const double* x, int64_t ldx, int64_t D,
+                                    const double* mean, const double* var, double* emis_out, int64_t ld) {
+  if (!h) return set_err(CV_EINVAL, "null handle");
+  if (nrows < 0) return set_err(CV_EINVAL, "nrows < 0");
+  if (ld < h->N) return set_err(CV_EINVAL, "ld = %lld is less than N = %d", (long long)ld, h->N);
+  cv_status st = gauss_args_ok(h, ldx, D, mean, var);
+  if (st != CV_OK) return st;
+  if (nrows > 0 && (!x || !emis_out)) return set_err(CV_EINVAL, "null argument");
+  if (nrows == 0) return CV_OK;
+  CV_LOCK(h);
+  if ((st = set_device(h)) != CV_OK) return st;
+  const hipStream_t stream = h->stream;
+  const size_t N = (size_t)h->N, Dd = (size_t)D, rows = (size_t)nrows;
+  if ((st = h->st_emis.ensure(rows * Dd * 8)) != CV_OK) return st;
+  if ((st = h->st_gamma.ensure(rows * N * 8)) != CV_OK) return st;
+  if (h->ws_rec) HIP_TRY(hipStreamWaitEvent(stream, h->ws_done, 0));
+  HIP_TRY(hipMemcpy2DAsync(h->st_emis.p, Dd * 8, x, (size_t)ldx * 8, Dd * 8, rows, hipMemcpyHostToDevice, stream));
+  const double* tab = nullptr;
+  if ((st = upload_gauss_tables(h, (int)D, mean, var, nullptr, stream, &tab)) == CV_OK)
+    st = launch_density(h, tab, h->st_emis.as<const double>(), D, (int)D, nrows, h->st_gamma.as<double>(), (int64_t)N, stream);
+  if (st == CV_OK) st = end_call(h, false, 0, stream);
+  if (st != CV_OK) {
+    (void)hipStreamSynchronize(stream);
+    return st;
+  }
+  HIP_TRY(hipMemcpy2DAsync(emis_out, (size_t)ld * 8, h->st_gamma.p, N * 8, N * 8, rows, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  return CV_OK;
+}
+
+// The gradient arm under densities computed per chunk, plus the moments: the counts request with
+// its Gaussian arm.
+CV_API cv_status cv_expected_counts_gauss_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
+                                                 const int64_t* offsets_dev, const double* x_dev, int64_t ldx, int64_t D,
+                                                 const double* mean, const double* var, const double* weight_dev,
+                                                 const double* center, const cv_opts* opts, double* loglik_dev,
+                                                 double* pi_cnt_dev, double* a_cnt_dev, double* g_cnt_dev,
+                                                 double* m1_dev, double* m2_dev, double* gamma_dev, uint8_t* status_dev) {
+  if (!h) return set_err(CV_EINVAL, "null handle");
+  if (nseq < 0) return set_err(CV_EINVAL, "nseq < 0");
+  if (!pi_cnt_dev || !a_cnt_dev || !g_cnt_dev || !m1_dev || !m2_dev) return set_err(CV_EINVAL, "null device buffer");
+  if (nseq > 0 && (!offsets_dev || !x_dev || !loglik_dev || !status_dev)) return set_err(CV_EINVAL, "null device buffer");
+  const cv_opts o = opts ? *opts : default_opts();
+  cv_status st = gauss_args_ok(h, ldx, D, mean, var);
+  if (st != CV_OK) return st;
+  if ((st = posterior_opts_ok(h, o)) != CV_OK) return st;
+  CV_LOCK(h);
+  if ((st = set_device(h)) != CV_OK) return st;
+  GaussReq gs{x_dev, ldx, (int)D, nullptr, g_cnt_dev, m1_dev, m2_dev};
+  const hipStream_t stream = call_stream(h, o);
+  if (nseq > 0 && (st = upload_gauss_tables(h, (int)D, mean, var, center, stream, &gs.tab)) != CV_OK) return st;
+  EmisSrc src{};
+  src.chunk_local = true;
+  CountsReq cnt{pi_cnt_dev, a_cnt_dev};
+  cnt.grad = true;
+  cnt.weight = weight_dev;
+  cnt.egrad = gamma_dev;
+  cnt.ld_grad = h->N;
+  cnt.gauss = &gs;
+  PostReq rq;
+  rq.loglik = loglik_dev;
+  rq.status = status_dev;
+  rq.stream = stream;
+  rq.emis = &src;
+  rq.cnt = &cnt;
+  return posterior_device(h, nseq, offsets_host, offsets_dev, nullptr, o, rq);
+}
+
+CV_API cv_status cv_expected_counts_gauss(cv_hmm* h, int64_t nseq, const int64_t* offsets, const double* x, int64_t ldx,
+                                          int64_t D, const double* mean, const double* var, const double* weight,
+                                          const double* center, const cv_opts* opts, double* loglik_out,
+                                          double* pi_cnt_out, double* a_cnt_out, double* g_cnt_out, double* m1_out,
+                                          double* m2_out, double* gamma_out, uint8_t* status_out) {
+  if (!h) return set_err(CV_EINVAL, "null handle");
+  if (nseq < 0 || !pi_cnt_out || !a_cnt_out || !g_cnt_out || !m1_out || !m2_out) return set_err(CV_EINVAL, "null argument");
+  if (nseq > 0 && (!offsets || !x || !loglik_out || !status_out)) return set_err(CV_EINVAL, "null argument");
+  const cv_opts o = opts ? *opts : default_opts();
+  cv_status st = gauss_args_ok(h, ldx, D, mean, var);
+  if (st != CV_OK) return st;
+  if ((st = posterior_opts_ok(h, o)) != CV_OK) return st;
+  HostOut out{loglik_out, status_out};
+  out.gamma = gamma_out;
+  out.pi_cnt = pi_cnt_out;
+  out.a_cnt = a_cnt_out;
+  out.grad = true;
+  out.weight = weight;
+  out.x = x;
+  out.ldx = ldx;
+  out.D = (int)D;
+  out.mean = mean;
+  out.var = var;
+  out.center = center;
+  out.g_cnt = g_cnt_out;
+  out.m1 = m1_out;
+  out.m2 = m2_out;
+  return host_entry(h, nseq, offsets, nullptr, nullptr, 0, o, out);
 }
 
 }  // extern "C"

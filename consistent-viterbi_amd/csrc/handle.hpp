@@ -250,6 +250,11 @@ struct cv_hmm {
   // sequence, and the host API's staging of pi_cnt [N] and a_cnt [N][N]
   DevBuf ps_xi_part, ps_xi_s, ps_g0, st_cnt;
   DevBuf ps_bc_acc, ps_bc_sort, ps_bc_part;  // cv_expected_counts_model*: [V][NP] accumulator, sort scratch, run sums
+  // cv_gauss_emissions* / cv_expected_counts_gauss*: the call's tables (c, mean^T, w^T, center) and
+  // their pinned staging; the moment GEMM's partial tiles, its [NP][2D + 1 padded] accumulator and
+  // the chunk's row flags
+  DevBuf ps_gauss, ps_gm_part, ps_gm_acc, ps_gm_ok;
+  OrderStage gs_pin;
   PinnedHost sm_pin;  // cv_sample_batch: the log-likelihoods and score planes on their way to the caller
   OrderStage ps_pin;
   // K-best workspace: the u16 back-pointers of one chunk, each sequence's last lists, the
@@ -461,9 +466,12 @@ T* rebased(T* p, int64_t e0, size_t width = 1) {
 
 // Caller-supplied emission scores (cv_decode_emissions*): a dense device array, row e (element
 // index of the CSR offsets) at p + e * ld, N log10 scores each.
+// chunk_local (cv_expected_counts_gauss*): p and ld are unused; the rows of a chunk are computed
+// into a workspace of the plan whose row 0 is the chunk's first element.
 struct EmisSrc {
   const double* p;
   int64_t ld;
+  bool chunk_local = false;
 };
 
 // The options of decode_device beyond a plain decode; every caller names only what it sets.

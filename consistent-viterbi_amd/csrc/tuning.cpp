@@ -31,7 +31,7 @@ const Key kKeys[] = {
     CVK_KEY(generic_wide_min), CVK_KEY(generic_prio), CVK_KEY(wide_s), CVK_KEY(ext_wide_min),
     CVK_KEY(chain_wide), CVK_KEY(chain_wide_min), CVK_KEY(f32_onebar), CVK_KEY(bw_global),
     CVK_KEY(bw_perseq), CVK_KEY(bw_gemm_path), CVK_KEY(bw_chunk_elems), CVK_KEY(bw_max_waves),
-    CVK_KEY(xi_part_rows), CVK_KEY(bcnt_part_rows),
+    CVK_KEY(xi_part_rows), CVK_KEY(bcnt_part_rows), CVK_KEY(gm_part_rows),
 };
 #undef CVK_KEY
 

@@ -99,6 +99,11 @@ struct Tuning {
                                // test hook: segments over many parts from a small input.  Not bit-identical
                                // either: it moves the boundaries of the runs, so the same terms are added in
                                // another grouping; b_cnt holds its bound under every value
+  // ---- Gaussian moments (kernels/gauss.hip) ----
+  int gm_part_rows = 0;        // > 0: rows per part of gm_gemm, rounded up to a multiple of 4 (0: by rule,
+                               // cvg::gm_part_rows); a test hook: several parts from a small input.  Not
+                               // bit-identical either: it regroups the sums; g_cnt, m1 and m2 hold their
+                               // bounds under every value
 };
 
 // the current call's tuning: the handle's snapshot inside a host API call, else the defaults

@@ -13,6 +13,8 @@ from .counts import (expected_counts, expected_counts_device, expected_counts_em
                      reestimate, reestimate_model)
 from .emissions import decode_emissions, decode_emissions_device  # noqa: F401
 from .grad import loglik_grad_emissions, loglik_grad_emissions_device  # noqa: F401
+from .gauss import (expected_counts_gauss, expected_counts_gauss_device, fit_gauss, gauss_emissions,  # noqa: F401
+                    gauss_emissions_device, gauss_hmm, reestimate_gauss)
 from . import autograd  # noqa: F401
 from .emissions import posterior_emissions, posterior_emissions_device, score_emissions  # noqa: F401
 from .fit import fit_mle, fit_train, last_fit_stats  # noqa: F401

@@ -50,6 +50,8 @@ EXPORTS = [
     "cv_expected_counts_emissions", "cv_expected_counts_emissions_device",
     "cv_loglik_grad_emissions", "cv_loglik_grad_emissions_device",
     "cv_expected_counts_model", "cv_expected_counts_model_device",
+    "cv_gauss_emissions", "cv_gauss_emissions_device",
+    "cv_expected_counts_gauss", "cv_expected_counts_gauss_device",
     "cv_sample_batch", "cv_sample_batch_device",
     "cv_last_t64_stats", "cv_last_fixed_first_stats", "cv_hmm_fit_last_stats",
     "cv_last_first_pass_kind", "cv_f32ru_trace", "cv_f32ru_trace_ragged",
@@ -148,6 +150,10 @@ def lib():
         "cv_loglik_grad_emissions_device": ([P, I64, P, P, P, I64, P, P, P, P, P, P, I64, P], S),
         "cv_expected_counts_model": ([P, I64, P, P, P, P, P, P, P, P, P, P], S),
         "cv_expected_counts_model_device": ([P, I64, P, P, P, P, P, P, P, P, P, P, P], S),
+        "cv_gauss_emissions": ([P, I64, P, I64, I64, P, P, P, I64], S),
+        "cv_gauss_emissions_device": ([P, I64, P, I64, I64, P, P, P, P, I64], S),
+        "cv_expected_counts_gauss": ([P, I64, P, P, I64, I64, P, P, P, P, P, P, P, P, P, P, P, P, P], S),
+        "cv_expected_counts_gauss_device": ([P, I64, P, P, P, I64, I64, P, P, P, P, P, P, P, P, P, P, P, P, P], S),
         "cv_last_timing": ([P, P], S),
         "cv_timing_begin": ([P], S),
         "cv_timing_end": ([P, P], S),

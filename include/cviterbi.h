@@ -261,6 +261,10 @@ CV_API void cv_hmm_destroy(cv_hmm* h);
  *                         gather (0: by rule, from the chunk's rows and NP); a test hook: segments over many
  *                         parts from a small input.  Not bit-identical: it regroups the sums; b_cnt holds
  *                         its bound under every value
+ *   gm_part_rows 0        cv_expected_counts_gauss*: > 0 the rows per part of the moment GEMM, rounded up
+ *                         to a multiple of 4 (0: by rule, from the chunk's rows, NP and D); a test hook:
+ *                         several parts from a small input.  Not bit-identical: it regroups the sums;
+ *                         g_cnt, m1 and m2 hold their bounds under every value
  * The bw_* keys are not bit-identical: the E-step sums are f64 atomic adds in arrival order, so
  * they hold to the fitting tolerance (1e-9 on the log10 parameters) instead.
  * Unknown keys and values outside int32 are CV_EINVAL.  cv_tuning_key(i) lists the keys
@@ -893,6 +897,107 @@ CV_API cv_status cv_expected_counts_model_device(cv_hmm* h, int64_t nseq, const 
                                                  const double* weight_dev, const cv_opts* opts, double* loglik_dev,
                                                  double* pi_cnt_dev, double* a_cnt_dev, double* b_cnt_dev,
                                                  double* gamma_dev, uint8_t* status_dev);
+
+/* ---- Gaussian emissions: log-densities and the E-step's statistics --------------------------
+ * A diagonal-covariance Gaussian HMM on raw observation vectors: the handle supplies (pi, A), its
+ * own b is ignored (as in the *_emissions entries), and per state j a mean[j * D + d] and a variance
+ * var[j * D + d] (host arrays [N][D], row-major, passed on every call: no handle state).  x holds
+ * the observations, element e (the element offsets of the CSR batch) at x + e * ldx, D values, f64,
+ * ldx >= D.  The emission score of element e in state j is
+ *   E[e][j] = log10 N(x_e; mean_j, var_j) = c_j - kappa q_ej,   q_ej = sum_d (x_ed - mean_jd)^2 w_jd,
+ *   w_jd = 1 / var_jd,   c_j = -1/2 sum_d log10(2 pi var_jd),   kappa = 0.5 / ln 10.
+ * cv_gauss_emissions writes emis_out[r * ld + j], j < N <= ld, for the rows r < nrows of x; the
+ * columns [N, ld) are never written.  The result feeds every *_emissions entry (decode, score,
+ * posterior, counts, gradients).
+ * How: the host computes w (one division per entry) and c_j (std::log10(2 pi var), summed in
+ * ascending d) in f64 and uploads them with the means to a handle-owned buffer
+ * (cv_hmm_release_workspaces frees it).  The kernel takes a state per lane: d = x - mean (one
+ * rounding), s = d d (one rounding), q = fma(s, w, q) in ascending d, E = c_j - kappa q -- the
+ * direct form, not x^2 - 2 x mean + mean^2, which cancels when |mean| >> sigma.  No reduction
+ * across lanes: host and device variants and repeated calls are bit-identical.
+ * Rows: a row of x that holds a NaN or +-inf is written as N NaNs (every *_emissions entry then
+ * flags its sequence CV_SEQ_BADOBS and leaves the others alone); a q that overflows gives -inf, a
+ * legal score.
+ * Numerics, with u = 2^-53 and c_abs_j = 1/2 sum_d |log10(2 pi var_jd)|:
+ *   |E - exact| <= (D + 8) u (kappa q + c_abs_j) + u |E|.
+ * D + 8: one rounding in d (two in s, relatively), one in s, one in w, one per fma step over
+ * non-negative terms, kappa and its product; for c_j one rounding per log and D - 1 of the plain
+ * sum; u |E|: the final subtraction (DESIGN.md "Gaussian emissions").
+ * Errors: CV_EINVAL for a null pointer, ldx < D, ld < N, D < 1, a non-finite mean, a variance that
+ * is NaN or outside [1e-300, 1e300] (the range keeps w normal); CV_ELIMIT for D > 1024.  They are
+ * checked before any device work.  N: whatever the handle holds (up to 65,535).
+ * Host pointers; synchronous. */
+CV_API cv_status cv_gauss_emissions(cv_hmm* h, int64_t nrows, const double* x, int64_t ldx, int64_t D,
+                                    const double* mean /*[N*D]*/, const double* var /*[N*D]*/,
+                                    double* emis_out /*[nrows][ld]*/, int64_t ld);
+/* The same with x_dev and emis_dev on the device (mean and var stay host pointers): enqueued on
+ * opts->stream (or the handle's stream; opts nullable, nothing else of it is read), returns after
+ * enqueueing. */
+CV_API cv_status cv_gauss_emissions_device(cv_hmm* h, int64_t nrows, const double* x_dev, int64_t ldx, int64_t D,
+                                           const double* mean, const double* var, const cv_opts* opts,
+                                           double* emis_dev, int64_t ld);
+/* The E-step of the Gaussian HMM.  By definition the call is cv_gauss_emissions followed by
+ * cv_loglik_grad_emissions on its result: loglik_out and status_out are that pair's, bit for bit,
+ * under any chunk plan; gamma_out (nullable, [L][N]: the rows w_s gamma_e, zeros for a sequence that
+ * is not OK) is that pair's emis_grad_out at ld_grad = N, bit for bit, under any chunk plan;
+ * pi_cnt_out and a_cnt_out are that pair's pi_grad_out and a_grad_out -- bit for bit when both calls
+ * run as one chunk, within that entry's bounds otherwise.  weight (nullable = all 1) as there.
+ * The three new outputs, over the elements e of the sequences with status CV_SEQ_OK, with
+ * g_e = w_s gamma_e and y_ed = x_ed - center_d (center: host [D], nullable = 0, y then exact):
+ *   g_cnt_out[j]       = sum_e g_e[j],
+ *   m1_out[j * D + d]  = sum_e g_e[j] y_ed,
+ *   m2_out[j * D + d]  = sum_e g_e[j] fl(y_ed^2),
+ * so that mean_j = center + m1 / g and var_j = m2 / g - (m1 / g)^2 (reestimate_gauss in Python).
+ * How: per chunk the density kernel fills a chunk-local [elements][NP] workspace, the staging and
+ * the forward pass read it as they read a caller's array, the gradient arm's backward pass puts the
+ * rows w_s gamma into gamma_out's device array or a workspace, and one f64 matrix-core GEMM forms
+ * M += G^T Phi, Phi = [1 | y | y^2] (2 D + 1 columns, formed on the fly from x, never stored), in
+ * parts -- fixed row ranges of the chunk, each part's tile stored whole, the parts folded in
+ * ascending order into one accumulator, chunks in stream order, no atomic adds -- and a last kernel
+ * writes the compact arrays.  The rows of a sequence that is not OK enter G and Phi as zeros by a
+ * select on the status (such a sequence may hold a NaN x or a NaN weight: harmless).  Results are
+ * bit-identical between two calls and between the host and device variants; g_cnt, m1 and m2 are
+ * NOT bit-identical across chunk plans (workspace_bytes) or part sizes (tuning key gm_part_rows),
+ * which regroup the sums -- the bounds hold for all of them.
+ * Numerics, with u = 2^-53, T the longest sequence of the call, L its elements, and X_abs the
+ * statistic computed from |w_s| and |y| ("exact": exact sums for the scores E as cv_gauss_emissions
+ * returns them):
+ *   |g_cnt - exact| <= (4 T (N + 8) + L + 1) u g_abs  + 1e-290 L max(1, max |w|) max(1, max |y|^2),
+ *   |m1 - exact|    <= (4 T (N + 8) + L + 3) u m1_abs + the same term,
+ *   |m2 - exact|    <= (4 T (N + 8) + L + 5) u m2_abs + the same term.
+ * The first is b_cnt's bound (gamma's bound, the weight, a signed sum of at most L terms); m1 adds
+ * the rounding of y and the product, m2 two more for the square (DESIGN.md "Gaussian emissions").
+ * opts, limits (N <= 4096), statuses and errors are those of cv_expected_counts_emissions, plus
+ * the argument errors of cv_gauss_emissions; a null pi_cnt_out, a_cnt_out, g_cnt_out, m1_out or
+ * m2_out is CV_EINVAL.  forced is honoured; the outputs are overwritten, not accumulated (nseq = 0
+ * writes zeros); the host variant returns CV_EINFEASIBLE after writing every output.
+ * Workspace: that of cv_loglik_grad_emissions, plus 8 NP bytes per element of a chunk (the
+ * densities), plus 8 NP bytes per element without gamma_out, plus the moment GEMM's partial tiles
+ * (8 NP W bytes per part, W = 2 D + 1 rounded up to a multiple of 16; at most 256 MiB and at most
+ * half of what the count GEMM's tiles leave of workspace_bytes, at least one part), all under
+ * workspace_bytes; beside them, on the handle, one NP x W accumulator, 4 bytes per element of a
+ * chunk (the row flags) and the tables (8 (N + 2 N D' + D') bytes, D' = D rounded up to 8, 16 or a
+ * multiple of 32).  cv_hmm_release_workspaces frees all of it.  cv_last_timing: fwd_ms covers the
+ * density kernel, bt_ms the moment kernels.  Host pointers; synchronous. */
+CV_API cv_status cv_expected_counts_gauss(cv_hmm* h, int64_t nseq, const int64_t* offsets, const double* x, int64_t ldx,
+                                          int64_t D, const double* mean /*[N*D]*/, const double* var /*[N*D]*/,
+                                          const double* weight /*[nseq], nullable = all 1*/,
+                                          const double* center /*[D], nullable = 0*/, const cv_opts* opts,
+                                          double* loglik_out /*[nseq]*/, double* pi_cnt_out /*[N]*/,
+                                          double* a_cnt_out /*[N*N] from-major*/, double* g_cnt_out /*[N]*/,
+                                          double* m1_out /*[N*D]*/, double* m2_out /*[N*D]*/,
+                                          double* gamma_out /*nullable [L*N]: w_s gamma*/,
+                                          uint8_t* status_out /*[nseq]*/);
+/* The same on device-resident buffers, with cv_expected_counts_emissions_device's contract:
+ * enqueued on opts->stream (or the handle's stream), returns after enqueueing; x_dev, weight_dev
+ * (nullable), gamma_dev (nullable) and the outputs are device pointers; mean, var and center stay
+ * host pointers (read before the call returns). */
+CV_API cv_status cv_expected_counts_gauss_device(cv_hmm* h, int64_t nseq, const int64_t* offsets_host,
+                                                 const int64_t* offsets_dev, const double* x_dev, int64_t ldx, int64_t D,
+                                                 const double* mean, const double* var, const double* weight_dev,
+                                                 const double* center, const cv_opts* opts, double* loglik_dev,
+                                                 double* pi_cnt_dev, double* a_cnt_dev, double* g_cnt_dev,
+                                                 double* m1_dev, double* m2_dev, double* gamma_dev, uint8_t* status_dev);
 
 /* ---- trait Solver (viterbi_solver.rs:11-16) -------------------------------------------
  * kind: "gpu"      f32 trellis kernel, VITERBI association, f64 re-scored objective
